@@ -1,15 +1,20 @@
 """Benchmark: rendered rays/s on SRN-cars 128x128 at 64 samples/ray (BASELINE.json metric, config C2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--images-per-step B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--images-per-step B] [--dump-outputs DIR] [--full]
 
 One step renders B novel 128x128 views of one held-out car per rank (default B = 16; 16384 rays
 each, 64 coarse samples per ray, srn-cars-code near 0.8 / far 1.8, lindepth, 4096-ray chunks)
 through the gfx950 path: ray bundle -> per-object code terms -> depths -> fused encode+MLP field
 kernel -> compositing, in the reference's precision (fp32: exact-product fp32 MFMA).  That is the
-headline ``value`` / ``dtype`` / ``roofline``.  Beside it, on the same batch: the opt-in 3xbf16
-field kernel (``bf16x3``, its own roofline against the bf16 MFMA peak), the C3 64+64 hierarchical
-render, the C4 chairs render sharded over the ranks, one C5 eval step and one C3 training
-iteration, and the CPU baseline.
+headline ``value`` / ``dtype`` / ``roofline``, and a plain run measures nothing else: it sets up,
+warms up, times the K steps and prints the result line.  ``--dump-outputs DIR`` also writes what the
+last timed step returned (the rendered pixels, float32) to ``DIR/rgb_coarse.npy``; the inputs are the
+same from run to run, so two builds can be compared pixel for pixel.  ``--full`` adds, on the same
+batch: the opt-in 3xbf16 field kernel (``bf16x3``, its own roofline against the bf16 MFMA peak) and the
+previous fp32 kernel, the C3 64+64 hierarchical render, the C4 chairs render sharded over the ranks,
+one C5 eval step and one C3 training iteration, the N-rank gather check, and the CPU baseline with
+the PSNR against it (``--no-cpu-baseline`` / ``--no-extras`` / ``--eval-iters 0`` / ``--train-iters 0``
+trim a full run).
 
 Ranks: under torch.distributed.run (WORLD_SIZE set) each process is one rank.  Otherwise
 ``--gpus N`` > 1 spawns N worker processes itself (as the reference's mp.spawn, train.py:159-179)
@@ -45,6 +50,7 @@ FOCAL = 131.25
 NC, NF = 64, 64
 NEAR, FAR = 0.8, 1.8
 CHUNK = 4096
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much
 FLOP_PER_SAMPLE = 572_416          # hoisted CodeNeRF MLP per sample-evaluation
 PEAK_FP32_MFMA_TFLOPS = 157.3      # MI355X dense fp32 matrix peak (MI355X_MICROARCH.md)
 PEAK_BF16_MFMA_TFLOPS = 2516.6     # MI355X dense bf16 matrix peak (guide: ~2.5 PF dense)
@@ -76,8 +82,14 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--images-per-step", type=int, default=16,
                     help="views of the car rendered per rank per step (16 x 16384 rays: ~90 ms of fp32 work)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline + bf16x3 only (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to DIR/rgb_coarse.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the other field-kernel formats, the side lines "
+                         "(perturbed, C3, C4, C5 eval, training), the N-rank gather check and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and PSNR")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: headline + the other field-kernel formats only (profiling runs)")
     ap.add_argument("--precision", default="f32", choices=sorted(KERNELS),
                     help="headline field-kernel arithmetic (f32 = the reference's precision)")
     ap.add_argument("--eval-iters", type=int, default=40,
@@ -280,28 +292,33 @@ def run(args):
         "build": {"cn_version": info["version"], "tree_src": info["tree_src"]},
     }
     psnr_img = {args.precision: img}
+    if args.dump_outputs and img is not None:
+        dump_outputs(args.dump_outputs, {"rgb_coarse": img})
 
-    # ---- the other field-kernel format on the same batch
-    other = "bf16x3" if args.precision == "f32" else "f32"
-    set_precision(other)
-    dto, fms_o, img_o = timed(args.steps, args.warmup, lambda rec: render_step(rec, True))
-    psnr_img[other] = img_o
-    result[other] = {"value": total_rays / dto, "unit": "rays/s", "ms_per_step": dto / args.steps * 1e3,
-                     "dtype": other, "roofline": roofline(other, fms_o),
-                     "note": ("opt-in 3-product bf16 split (Wh.Xh + Wh.Xl + Wl.Xh, fp32 accumulate): narrower than "
-                              "the reference's fp32; parity-tested at the same tolerances incl. trained-magnitude "
-                              "weights (tests/test_gpu_configs.py)") if other == "bf16x3" else "reference precision"}
-    if args.precision == "f32":
-        # the previous fp32 kernel (32x32x2, one wave per SIMD; still the training forward)
-        set_precision("f32_v1")
-        dtv, fms_v, img_v = timed(args.steps, args.warmup, lambda rec: render_step(rec, True))
-        psnr_img["f32_v1"] = img_v
-        result["f32_v1"] = {"value": total_rays / dtv, "unit": "rays/s", "ms_per_step": dtv / args.steps * 1e3,
-                            "dtype": "f32", "roofline": roofline("f32_v1", fms_v),
-                            "note": "round-1 fp32 kernel, kept as the forward of the layer-wise training path (models whose inference and training precisions differ)"}
-    set_precision(args.precision)
+    if args.full:
+        # ---- the other field-kernel format on the same batch
+        other = "bf16x3" if args.precision == "f32" else "f32"
+        set_precision(other)
+        dto, fms_o, img_o = timed(args.steps, args.warmup, lambda rec: render_step(rec, True))
+        psnr_img[other] = img_o
+        result[other] = {"value": total_rays / dto, "unit": "rays/s", "ms_per_step": dto / args.steps * 1e3,
+                         "dtype": other, "roofline": roofline(other, fms_o),
+                         "note": ("opt-in 3-product bf16 split (Wh.Xh + Wh.Xl + Wl.Xh, fp32 accumulate): narrower "
+                                  "than the reference's fp32; parity-tested at the same tolerances incl. "
+                                  "trained-magnitude weights (tests/test_gpu_configs.py)") if other == "bf16x3"
+                         else "reference precision"}
+        if args.precision == "f32":
+            # the previous fp32 kernel (32x32x2, one wave per SIMD; still the training forward)
+            set_precision("f32_v1")
+            dtv, fms_v, img_v = timed(args.steps, args.warmup, lambda rec: render_step(rec, True))
+            psnr_img["f32_v1"] = img_v
+            result["f32_v1"] = {"value": total_rays / dtv, "unit": "rays/s", "ms_per_step": dtv / args.steps * 1e3,
+                                "dtype": "f32", "roofline": roofline("f32_v1", fms_v),
+                                "note": "round-1 fp32 kernel, kept as the forward of the layer-wise training path "
+                                        "(models whose inference and training precisions differ)"}
+        set_precision(args.precision)
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # ---- C2 as srn-cars-code.yml's validation render configures it (perturb: True, Q4): stratified
         # depths from the device RNG (torch.rand_like on the GPU, point_sampler.py:61-65)
         ps_p = PointSampler(NC, NF, NEAR, FAR, "lindepth", True, torch.float32, dev)
@@ -347,9 +364,9 @@ def run(args):
             result["train_cars_code"] = train_bench(dev, k, args.train_iters, world, "f32", shape="cars_code")
             result["train_3080"] = train_bench(dev, k, 4 * args.train_iters, world, "f32", shape="3080")
 
-    if world > 1 and rank == 0 and psnr_img[args.precision] is not None:
+    if args.full and world > 1 and rank == 0 and psnr_img[args.precision] is not None:
         result.update(multi_rank_check(psnr_img[args.precision], rs, poses[:1], per, zs, zt, ps, emb, models))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU baseline: rank 0 at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU baseline: rank 0 at N=1 only
         cb, ref_img = cpu_baseline(k, poses[:1])
         result["cpu_baseline"] = cb
         from oracle.codenerf_oracle import mse2psnr
@@ -362,6 +379,20 @@ def run(args):
     if world > 1:
         dist.destroy_process_group()
     return result if rank == 0 else None
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the last timed step returned (rank 0 holds it), one float32 ``<name>.npy`` each;
+    of an output above DUMP_MAX_BYTES, a fixed (seeded) sample of its rows, in row order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            rows = budget // (a.nbytes // a.shape[0])
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def multi_rank_check(img, rs, pose1, per, zs, zt, ps, emb, models):

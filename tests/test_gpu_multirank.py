@@ -222,7 +222,8 @@ def _bench_worker(rank, world, rdv, out_dir, argv=_BENCH_HEADLINE):
                       CODENERF_INIT_METHOD=rdv)
     sys.path.insert(0, ROOT)
     import bench
-    res = bench.run(bench.parse_args(list(argv) + ["--no-cpu-baseline", "--backend", "gloo", "--quiet"]))
+    # --full: the gather check and the side lines these tests read are not part of a plain run
+    res = bench.run(bench.parse_args(list(argv) + ["--full", "--no-cpu-baseline", "--backend", "gloo", "--quiet"]))
     if rank == 0:
         with open(os.path.join(out_dir, "bench.json"), "w") as f:
             json.dump(res, f)

@@ -110,6 +110,27 @@ def test_bench_refuses_more_gpus_than_visible():
     assert "needs 64 visible GPUs" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_float32_and_capped(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 <name>.npy per output, whole when it fits the byte cap,
+    else the same (seeded) sample of its rows, in row order, on every call."""
+    import os
+    import sys
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    assert bench.DUMP_MAX_BYTES <= 64 * 1000 * 1000
+    img = torch.arange(300 * 3, dtype=torch.float64).reshape(300, 3)
+    bench.dump_outputs(str(tmp_path / "a"), {"rgb_coarse": img})
+    a = np.load(tmp_path / "a" / "rgb_coarse.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, img.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100 * 12)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"rgb_coarse": img})
+    b, c = (np.load(tmp_path / d / "rgb_coarse.npy") for d in ("b", "c"))
+    assert b.shape == (100, 3) and b.dtype == np.float32 and np.array_equal(b, c)
+    assert (np.diff(b[:, 0]) > 0).all() and np.array_equal(b, a[(b[:, 0] / 3).astype(int)])
+
+
 def test_code_grad_sink_claims_zeroed_slots_once():
     """CodeGradSink (the in-place code-gradient rows): it claims the tables' zeroed optimiser slots only
     when every table is trainable, has no .grad yet and carries a slot; it hands out row k of each;

@@ -14,6 +14,6 @@ VT_RAYS=6144 VT_ITERS=${VT_ITERS:-20} timeout -k 10 200 python tools/variant_tim
 rc=$?; echo "variants rc=$rc"; cat $O/variants.jsonl; [ $rc -ne 0 ] && { tail -5 $O/variants.err; exit $rc; }
 [ -n "$NO_BENCH" ] && exit 0
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline ${BENCH_ARGS} > $O/bench.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline ${BENCH_ARGS} > $O/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -1 $O/bench.log | cut -c1-3000; [ $rc -ne 0 ] && exit $rc
 python $R/tools/kstats.py $O/prof/run_kernel_stats.csv > $O/kstats.txt; head -30 $O/kstats.txt
