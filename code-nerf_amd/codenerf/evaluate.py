@@ -504,8 +504,11 @@ def validate(cfg, val_data: Dict[str, torch.Tensor], models, samplers, embedders
         e.val_iterations, val_lr=o.val_lr, angle_lr=_pose_lr(o, "angle_lr"), radius_lr=_pose_lr(o, "radius_lr"),
         regularizer_lambda=e.regularizer_lambda, optimizer=getattr(o, "val_type", "AdamW"), log_every=log_every,
         gt_pose=gt_pose, shard_rays=shard_rays)
+    # nerf.validation.coarse_density (default False): the view's coarse pass on the density kernel
+    # (parallel_image_render's coarse_rgb=False; rgb_fine has the same bits either way)
+    coarse_density = bool(getattr(cfg.nerf.validation, "coarse_density", False))
     rgb = nerf.parallel_image_render(cfg, cam_pose, [zs.detach(), zt.detach()], models, samplers, embedders,
-                                     device)
+                                     device, coarse_rgb=not coarse_density)
     out = {"history": history, "rgb": rgb, "codes": (zs.detach(), zt.detach()),
            "pose": (th.detach().item(), ph.detach().item(), rh.detach().item()), "cam_pose": cam_pose}
     rank0 = (not is_distributed) or dist.get_rank() == 0

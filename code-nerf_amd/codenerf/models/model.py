@@ -112,6 +112,34 @@ class CodeNeRFModel(torch.nn.Module):
         return ops.mlp_forward(self.packed(), cb, x, index, precision=self.kernel_format())
 
 
+    def density(self, z_s: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """sigma_raw of ``forward`` alone (model.py:174-186), which reads neither the view direction
+        columns nor a texture code: per-row (or expanded) shape codes (M, 256) and encoded rows
+        (M, 63) or (M, 90) -> (M,).  Inference only (the density kernel has no backward)."""
+        self._require_supported()
+        codes_s, _, _ = _dedupe_codes(z_s, z_s)
+        cb = density_code_bias(self, codes_s)
+        return ops.density_field(self.packed(), cb, _FREQS_UNUSED, x=x)
+
+
+# encoded rows carry their frequencies already: cn_density_field reads none in that mode
+_FREQS_UNUSED = (0.0,) * 10
+
+
+def density_code_bias(m, cs: torch.Tensor) -> torch.Tensor:
+    """The code terms the density kernel reads, for shape code rows ``cs`` (n, 256): cn_code_bias with a
+    zero texture row (its layer_xyz2 and sigma entries depend on the shape code alone).  Raises for a
+    model whose precision does not run the fp32 16x16x4 field kernel -- the only one with a density
+    form -- instead of computing in another arithmetic."""
+    fmt = m.kernel_format()
+    if fmt != "f32_w16":
+        raise NotImplementedError(
+            f"the density kernel exists for the fp32 field kernel only (precision 'f32'); this model runs "
+            f"precision {m.precision!r} (kernel format {fmt!r})")
+    cs = cs.detach()
+    return m.code_bias(cs, torch.zeros_like(cs))
+
+
 def _field_op(m: CodeNeRFModel, cs, ct, rd, chunk_rows, fx, fd, pts=None, ro=None, z=None, code_index=None,
               pair=None):
     """The fused radiance field (encode + MLP) of ``m`` on distinct code rows cs / ct (``pair``: the render's

@@ -25,7 +25,7 @@ from .volumetric_render import volume_render
 
 __all__ = ["RaySampler", "PointSampler", "PositionalEmbedder", "volume_render", "prepare_samplers",
            "prepare_embedders", "predict_radiance_and_render", "forward_pass", "parallel_image_render",
-           "render_rays", "gather_rows", "gather_views"]
+           "render_rays", "gather_rows", "gather_views", "density", "density_grid"]
 
 
 def prepare_samplers(cfg, height: int, width: int, intrinsics, datatype, device) -> Tuple[RaySampler, PointSampler]:
@@ -102,6 +102,70 @@ def _field(model, embedders, rd, z_s, z_t, chunk_rows, pts=None, ro=None, z=None
                      pair=pair)
 
 
+def _density_field_raw(model, embedders, rd, z_s, z_t, chunk_rows, pts=None, ro=None, z=None, pair=None):
+    """_field's signature on the density kernel: raw rows [0, 0, 0, sigma_raw] (render_rays'
+    coarse_rgb=False).  No gradient path, and no chunk_rows: density has no view direction (Q1)."""
+    from ..models.model import density_code_bias
+    fx, _ = _check_embedders(embedders)
+    cs, _, code_index = _codes(z_s, z_t)
+    m = _unwrap(model)
+    with torch.no_grad():
+        cb = density_code_bias(m, cs)
+        return ops.density_field(m.packed(), cb, fx, pts=pts, ro=None if pts is not None else ro,
+                                 rd=None if pts is not None else rd, z=None if pts is not None else z,
+                                 code_index=code_index, want_sigma=False, want_raw=True)
+
+
+def density(model, embedders, pts: torch.Tensor, z_s: torch.Tensor) -> torch.Tensor:
+    """sigma_raw (model.py:174-186) at points of any leading shape (..., 3) for one shape code (1, 256) or
+    one per row of the first dimension (pts.shape[0], 256) -> sigma_raw of the leading shape.  No view
+    direction and no texture code enter a density.  Inference only."""
+    from ..models.model import density_code_bias
+    fx, _ = _check_embedders(embedders)
+    assert pts.shape[-1] == 3, "pts must be (..., 3)"
+    lead = tuple(pts.shape[:-1])
+    n = lead[0] if lead else 1
+    per_row = 1
+    for k in lead[1:]:
+        per_row *= k
+    assert z_s.dim() == 2 and z_s.shape[0] in (1, n), "z_s must be (1, C) or one row per pts.shape[0]"
+    m = _unwrap(model)
+    with torch.no_grad():
+        if z_s.shape[0] > 1 and z_s.stride(0) == 0:
+            z_s = z_s[:1]
+        cb = density_code_bias(m, z_s)
+        sigma = ops.density_field(m.packed(), cb, fx, pts=pts.detach().reshape(n, per_row, 3))
+    return sigma.reshape(lead)
+
+
+def density_grid(model, embedders, z_s: torch.Tensor, resolution: int, bound: float, activated: bool = True,
+                 max_points: int = 1 << 22) -> torch.Tensor:
+    """The density of one shape code (1, 256) on a regular grid -- the input of an iso-surface
+    extraction -> (D, D, D), D = ``resolution``, axis order [ix, iy, iz], the points
+    ``linspace(-bound, bound, D)`` per axis (``meshgrid(indexing="ij")``), evaluated in slabs of at
+    most ``max_points`` points.  ``activated``: softplus(sigma_raw - 1), the density the renderer
+    integrates (volumetric_render.py:32); else sigma_raw."""
+    from ..models.model import density_code_bias
+    fx, _ = _check_embedders(embedders)
+    d = int(resolution)
+    assert d >= 1 and max_points >= 1 and z_s.dim() == 2 and z_s.shape[0] == 1, \
+        "density_grid takes one shape code (1, C) and a positive resolution"
+    m = _unwrap(model)
+    with torch.no_grad():
+        cb = density_code_bias(m, z_s)
+        packed = m.packed()
+        dev = cb.device
+        lin = torch.linspace(-bound, bound, d, dtype=torch.float32, device=dev)
+        out = torch.empty(d * d * d, dtype=torch.float32, device=dev)
+        for start in range(0, d * d * d, max_points):
+            k = torch.arange(start, min(start + max_points, d * d * d), device=dev)
+            pts = torch.stack((lin[k // (d * d)], lin[(k // d) % d], lin[k % d]), dim=-1)
+            out[start:start + k.numel()] = ops.density_field(packed, cb, fx, pts=pts)
+        if activated:
+            out = torch.nn.functional.softplus(out - 1.0)
+    return out.view(d, d, d)
+
+
 def forward_pass(model, embedders, rd: torch.Tensor, pts: torch.Tensor,
                  object_embedding: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
     """nerf/__init__.py:94-134: embed + MLP for one chunk -> (R, S, 4).
@@ -117,7 +181,8 @@ def forward_pass(model, embedders, rd: torch.Tensor, pts: torch.Tensor,
 def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torch.Tensor,
                 point_sampler: PointSampler, embedders, coarse_model, fine_model=None, chunk_rows: Optional[int] = None,
                 t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
-                coarse_only: bool = False, events: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+                coarse_only: bool = False, events: Optional[dict] = None,
+                coarse_rgb: bool = True) -> Dict[str, torch.Tensor]:
     """predict_radiance_and_render over a whole ray list, chunk semantics kept via ``chunk_rows``.
 
     Returns rgb/depth/acc for the coarse pass (+ weights) and, unless
@@ -125,13 +190,25 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     predict_radiance_and_render on every ``chunk_rows`` slice and concatenating.
     ``events`` (bench instrumentation): a dict that receives (start, end)
     torch.cuda.Event pairs around each field-kernel launch under key "field".
+    ``coarse_rgb=False`` (inference only): the coarse pass exists to give ``weights_coarse`` to the
+    resampling, which read densities alone, so the coarse field runs the density kernel (raw rows
+    [0, 0, 0, sigma_raw], the same sigma bits) and the result has no "rgb_coarse"; everything else
+    in it is bitwise the default call's.
     """
-    def timed_field(*a, **kw):
+    if not coarse_rgb:
+        if torch.is_grad_enabled() and (
+                any(t is not None and t.requires_grad for t in (ro, rd, z_s, z_t)) or
+                any(p.requires_grad for m in (coarse_model, fine_model) if m is not None
+                    for p in _unwrap(m).param_list())):
+            raise ValueError("coarse_rgb=False is the inference render: the density kernel has no backward "
+                             "(render under torch.no_grad(), or keep coarse_rgb=True)")
+
+    def timed_field(*a, field=_field, **kw):
         if events is None:
-            return _field(*a, **kw)
+            return field(*a, **kw)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        r = _field(*a, **kw)
+        r = field(*a, **kw)
         e1.record()
         events.setdefault("field", []).append((e0, e1))
         return r
@@ -144,7 +221,7 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     _, z_c = ops.sample_uniform(ro.detach(), rd.detach(), ps.z_vals, ps.lower, ps.upper,
                                 t_rand if ps.perturb else None, want_pts=False)
     pair = None
-    if fine_model is not None and not coarse_only:
+    if fine_model is not None and not coarse_only and coarse_rgb:
         # the two differentiable fields' pre-field launches (code terms, packs, zeroed accumulators) as
         # one launch; each field takes its part (no launch when either runs without gradients)
         from ..autograd import new_field_pair, prefetch_render_prepares
@@ -156,10 +233,13 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
                                  ps.num_samples_coarse + ps.num_samples_fine, chunk_rows, fx, fd, code_index)
     # pts = ro + rd z is formed inside the field kernel (z detached, point_sampler.py:115); with
     # gradients on, the field's backward returns d ro / d rd through both the points and the view dirs
-    raw_c = timed_field(coarse_model, embedders, rd, z_s, z_t, chunk_rows, ro=ro, z=z_c, pair=pair)
+    raw_c = timed_field(coarse_model, embedders, rd, z_s, z_t, chunk_rows, ro=ro, z=z_c, pair=pair,
+                        field=_field if coarse_rgb else _density_field_raw)
     rgb_c, disp_c, acc_c, w_c, depth_c = volume_render(raw_c, z_c, rd)
     out = {"rgb_coarse": rgb_c, "disp_coarse": disp_c, "acc_coarse": acc_c, "weights_coarse": w_c,
            "depth_coarse": depth_c, "z_coarse": z_c}
+    if not coarse_rgb:
+        del out["rgb_coarse"]       # composited from zero colours: not a result
     if coarse_only:
         return out
     if ps.perturb and u is None:
@@ -183,7 +263,8 @@ def predict_radiance_and_render(rays: Tuple[torch.Tensor, torch.Tensor], point_s
 
 
 def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, samplers, embedders, device,
-                          key: str = "rgb_fine", coarse_only: bool = False) -> Optional[torch.Tensor]:
+                          key: str = "rgb_fine", coarse_only: bool = False,
+                          coarse_rgb: bool = True) -> Optional[torch.Tensor]:
     """nerf/__init__.py:137-226: shard the image's rays over ranks, render, gather on rank 0.
 
     The split is the reference's (Q5: truncating, the last rank takes the
@@ -191,7 +272,11 @@ def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, sam
     reference's chunking (``cfg.nerf.validation.chunksize``) kept as Q1
     semantics; one all-gather (RCCL over xGMI on MI355X) of the padded
     per-rank rows.  Rank 0 returns (H*W, 3); the others return None.
+    ``coarse_rgb=False``: the coarse pass computes densities only (render_rays); ``key`` cannot then
+    be "rgb_coarse".
     """
+    if not coarse_rgb and key == "rgb_coarse":
+        raise ValueError('coarse_rgb=False renders no coarse colours: key="rgb_coarse" needs coarse_rgb=True')
     rank = 0
     is_distributed = bool(getattr(cfg, "is_distributed", False))
     n_gpus = int(getattr(cfg, "gpus", 1))
@@ -212,7 +297,7 @@ def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, sam
         z_t = z_t.to(device).expand(num_rays, -1)[sl]
         out = render_rays(ro[sl].to(device), rd[sl].to(device), z_s, z_t, point_sampler, embedders,
                           models["nerf_coarse"], models.get("nerf_fine"), cfg.nerf.validation.chunksize,
-                          coarse_only=coarse_only)
+                          coarse_only=coarse_only, coarse_rgb=coarse_rgb)
         rgb = out[key]
         if not is_distributed:
             return rgb

@@ -426,6 +426,58 @@ def radiance_field(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int, chunk
     return raw
 
 
+def density_field(packed: Tensor, cb: Tensor, freqs_xyz: Sequence[float], *, pts: Optional[Tensor] = None,
+                  ro: Optional[Tensor] = None, rd: Optional[Tensor] = None, z: Optional[Tensor] = None,
+                  x: Optional[Tensor] = None, code_index: Optional[Tensor] = None, want_sigma: bool = True,
+                  want_raw: bool = False):
+    """sigma_raw of CodeNeRFModel.forward alone (model.py:174-186; cn_density_field): the fp32 field
+    kernel's first 10 weight chunks, bitwise the sigma_raw radiance_field gives for the same points.
+
+    Exactly one input: ``pts`` (R, S, 3) or (M, 3) [R = M, S = 1]; ``ro``, ``rd`` (R, 3) with ``z`` (R, S);
+    ``x`` (M, 63) or (M, 90) encoded rows [R = M, S = 1].  ``packed``: the "f32_w16" pack; ``cb`` one code
+    row, one per R, or rows picked by ``code_index`` (R,) (the texture half of ``cb`` is not read).
+    -> sigma (R, S) / (M,), or raw (.., 4) rows [0, 0, 0, sigma_raw] (what volume_render and
+    sample_pdf take), or (sigma, raw) when both are asked for."""
+    lib = _lib_ready()
+    assert want_sigma or want_raw, "ask for sigma, raw or both"
+    modes = (pts is not None) + (x is not None) + (ro is not None or rd is not None or z is not None)
+    assert modes == 1, "give exactly one of pts, (ro, rd, z) and x"
+    x_stride = 0
+    if pts is not None:
+        pts = _cuda(pts, "pts")
+        assert pts.dim() in (2, 3) and pts.shape[-1] == 3, "pts must be (num_rays, num_samples, 3) or (M, 3)"
+        lead = tuple(pts.shape[:-1])
+        dev = pts.device
+    elif x is not None:
+        x = _cuda(x, "x")
+        assert x.dim() == 2 and x.shape[1] in (63, 90), "x must be (M, 63) or (M, 63 + 27)"
+        lead, x_stride, dev = (x.shape[0],), x.shape[1], x.device
+    else:
+        assert ro is not None and rd is not None and z is not None, "the ray form takes ro, rd and z"
+        ro, rd, z = _cuda(ro, "ro"), _cuda(rd, "rd"), _cuda(z, "z")
+        assert z.dim() == 2 and ro.shape == (z.shape[0], 3) and rd.shape == (z.shape[0], 3), \
+            "ro / rd must be (num_rays, 3) and z (num_rays, num_samples)"
+        lead, dev = tuple(z.shape), z.device
+    n = lead[0]
+    s = lead[1] if len(lead) == 2 else 1
+    n_codes = cb.shape[0]
+    if code_index is not None:
+        code_index = _cuda(code_index, "code_index", torch.int64)
+        assert code_index.shape == (n,), "code_index must be (num_rays,)"
+    else:
+        assert n_codes in (1, n), "codes must be one row or one row per ray"
+    assert len(freqs_xyz) == 10, "the field kernel implements L_xyz=10"
+    sigma = torch.empty(lead, device=dev, dtype=torch.float32) if want_sigma else None
+    raw = torch.empty(lead + (4,), device=dev, dtype=torch.float32) if want_raw else None
+    if n * s:      # no samples: empty outputs without a launch (the C ABI refuses sizes of 0)
+        check(lib.cn_density_field(ptr(packed), _lib.CN_FMT_F32_W16, ptr(cb), ptr(code_index), n_codes, ptr(pts),
+                                   ptr(ro), ptr(rd), ptr(z), ptr(x), x_stride, n, s, _lib.host_floats(freqs_xyz),
+                                   ptr(sigma), ptr(raw), stream_of(cb)), "cn_density_field")
+    if want_sigma and want_raw:
+        return sigma, raw
+    return sigma if want_sigma else raw
+
+
 # ------------------------------------------------------------------ backward (A14)
 
 

@@ -9,7 +9,7 @@ with torch.compile's fake-tensor tracing like any aten op.
     rgb, disp, acc, w, depth = torch.ops.codenerf.volume_render(raw, z, rd)
 
 Ops: ray_bundle, sample_uniform, sample_pdf, posenc, codenerf_mlp (inference,
-either precision), codenerf_mlp_train (fp32 + saved activations,
+either precision), density_field (sigma_raw alone, inference), codenerf_mlp_train (fp32 + saved activations,
 differentiable), volume_render, render_rays (the fused coarse -> resample ->
 fine pipeline of predict_radiance_and_render), and the *_backward ops.
 """
@@ -189,6 +189,29 @@ def codenerf_mlp(z_s: Tensor, z_t: Tensor, x: Tensor, params: List[Tensor], prec
 @codenerf_mlp.register_fake
 def _(z_s, z_t, x, params, precision="f32"):
     return x.new_empty(x.shape[0], 4)
+
+
+class _Freqs:
+    """What codenerf.nerf reads of a PositionalEmbedder: the log-sampled frequencies, inputs included."""
+
+    def __init__(self, num_freq: int):
+        self.num_freq, self.include_input, self.freqs = num_freq, True, [2.0 ** k for k in range(num_freq)]
+
+
+_DENSITY_EMBEDDERS = (_Freqs(10), _Freqs(4))
+
+
+@_op("density_field")
+def density_field(z_s: Tensor, pts: Tensor, params: List[Tensor]) -> Tensor:
+    """sigma_raw alone (model.py:174-186) at points (..., 3) for one shape code (1, 256) or one per row of
+    the first dimension; params in state_dict order -> the leading shape.  fp32 kernel; not differentiable."""
+    from . import nerf
+    return nerf.density(_ParamModel(params, "f32"), _DENSITY_EMBEDDERS, pts, z_s)
+
+
+@density_field.register_fake
+def _(z_s, pts, params):
+    return pts.new_empty(pts.shape[:-1])
 
 
 @_op("codenerf_mlp_train")

@@ -55,6 +55,14 @@ struct FieldArgs {
   int64_t n_blocks;      // set by the backward launchers: the grid they launched
 };
 
+// The density-only forward (cn_density_field): the field's inputs (f.raw optional here; f.x rows
+// x_stride floats apart, only their 63 xyz columns read) and the (m) sigma output (optional).
+struct DensityArgs {
+  FieldArgs f;
+  float* sigma;
+  int64_t x_stride;
+};
+
 // The most workgroups a fused backward launches in the deterministic form, and its most waves per
 // workgroup (gc_part holds kMaxBwdBlocks x kMaxBwdWaves rows).
 constexpr int64_t kMaxBwdBlocks = 512, kMaxBwdWaves = 8;
@@ -294,6 +302,7 @@ int launch_field_x3_bwd(int mode, FieldArgs& a, hipStream_t st);
 int64_t packed_floats_w16();
 int launch_pack_w16(const Params& P, float* packed, hipStream_t st);
 int launch_field_w16(int mode, FieldArgs& a, hipStream_t st);  // a.masks: also the ReLU masks
+int launch_density_w16(int mode, DensityArgs& d, hipStream_t st);  // sigma only: the stream's first 10 chunks
 int64_t mask_words_w16(int64_t m);
 int launch_pack_w16t(const Params& P, float* packed, hipStream_t st);
 // code_bias + the CN_FMT_F32_W16 / _T packs + a zeroed buffer (any of them null: skipped), for one or

@@ -235,18 +235,29 @@ __device__ __forceinline__ int stream_src_ng(const State& s, int cn) {
   if (k >= kNoGeoChunks) k -= kNoGeoChunks;
   return k + (k >= kNoGeoSkip ? 1 : 0);
 }
+// SIGMA: the density-only forward streams the pack's first kSigmaChunks chunks (layer_xyz1,
+// layer_xyz2) per tile; 10 is not a multiple of the ring either, so its counter runs on the same way.
+constexpr int kSigmaChunks = kCL3;
+__device__ __forceinline__ int stream_src_sigma(const State& s, int cn) {
+  const int k = cn - s.cbase;
+  return k >= kSigmaChunks ? k - kSigmaChunks : k;
+}
+// Which stream a chunk counter walks (dma_piece): a bool NOGEO converts to the first two.
+constexpr int kStreamFull = 0, kStreamNG = 1, kStreamSigma = 2;
 
 // One LDS-DMA piece: 1 KiB of chunk cn (piece p of 4 for this wave).
-template <bool NG = false>
+template <int NG = kStreamFull>
 __device__ __forceinline__ void dma_piece(const State& s, float4* lds, int cn, int p) {
-  const int src = NG ? stream_src_ng(s, cn) : (cn < kChunks ? cn : cn - kChunks);
+  const int src = NG == kStreamSigma ? stream_src_sigma(s, cn)
+                  : NG == kStreamNG  ? stream_src_ng(s, cn)
+                                     : (cn < kChunks ? cn : cn - kChunks);
   const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(src * kChunkQuads + p * 64 * kWaves) * 16u);
   __builtin_amdgcn_raw_ptr_buffer_load_lds(
       s.wsrc, (lds_ptr_t)(lds + (cn & (kRing - 1)) * kChunkQuads + p * 64 * kWaves + s.wave * 64), 16, s.voff,
       soff, 0, 0);
 }
 
-template <bool NG = false>
+template <int NG = kStreamFull>
 __device__ __forceinline__ void dma_chunk(const State& s, float4* lds, int cn) {
 #pragma unroll
   for (int p = 0; p < kPiecesPerWave; ++p) dma_piece<NG>(s, lds, cn, p);
@@ -318,7 +329,7 @@ struct NoPost {
 // r03g: SQ_WAIT_INST_ANY +77 M and SQ_WAIT_ANY +55 M quad-cycles over the mask-only forward for
 // 2.09 M stores); two per chunk they overlap the MFMAs.  They follow the chunk's DMA, so the next
 // barrier's counted vmcnt still sees the ring's pieces in order.
-template <int NS, int CI = 0, bool NG = false, typename GetB, typename Post = NoPost>
+template <int NS, int CI = 0, int NG = kStreamFull, typename GetB, typename Post = NoPost>
 __device__ __forceinline__ void chunk16(State& s, float4* lds, int c, GetB getb, Post post = Post{}) {
   const float4* slot = lds + (c & (kRing - 1)) * kChunkQuads + s.lane;
   const float4* nslot = lds + ((c + 1) & (kRing - 1)) * kChunkQuads + s.lane;
@@ -436,7 +447,7 @@ struct LazyXyz {
 };
 
 // A 256-input layer: 8 chunks, B from s.act.
-template <bool NG = false, typename Post = NoPost>
+template <int NG = kStreamFull, typename Post = NoPost>
 __device__ __forceinline__ void layer256(State& s, float4* lds, int& c, Post post = Post{}) {
   chunk16<8, 0, NG>(s, lds, c + 0, ActB<0>{s}, post);
   chunk16<8, 1, NG>(s, lds, c + 1, ActB<8>{s}, post);
@@ -568,6 +579,31 @@ struct XencStore {
   }
 };
 
+// sigma = fc_out row 0 . [h2, zs2] + b: the h2 part (s.act = h2, this lane group's 64 features), the
+// code part from cn_code_bias (two packed chains: 32 v_pk_fma_f32 instead of one 64-deep fmaf chain)
+__device__ __forceinline__ float sigma_partial(const State& s, const float* clds) {
+  typedef float float2v __attribute__((ext_vector_type(2)));
+  // the weights in two batches of 8 LDS reads issued together (one wait per batch; read one at
+  // a time, each FMA pair waited on its own read while both waves of the SIMD sat here)
+  float2v s0{0.0f, 0.0f}, s1{0.0f, 0.0f};
+  const floatx4* wsig = reinterpret_cast<const floatx4*>(clds + kCSig) + 16 * fresh(s.g);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    floatx4 w[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[k] = wsig[8 * h + k];
+    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int ob = 8 * h + k;
+      s0 = __builtin_elementwise_fma(float2v{w[k][0], w[k][1]}, float2v{s.act[ob][0], s.act[ob][1]}, s0);
+      s1 = __builtin_elementwise_fma(float2v{w[k][2], w[k][3]}, float2v{s.act[ob][2], s.act[ob][3]}, s1);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);
+  }
+  return (s0[0] + s0[1]) + (s1[0] + s1[1]);
+}
+
 // Training forward: the post-activation rows the weight gradients read (h1, h2, feat, v1, v2 as
 // (5, m, 256) planes, feature 16 ob + 4 g + r: one 16-B store per block per lane).
 
@@ -695,28 +731,7 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
     const LayerStores<MASKS, SAVE> st{s, a, tile, layer == kXyz2 ? 0 : (layer == kOut ? 1 : (layer == kDir2 ? 2 : -1)),
                                      layer - kXyz2, mw};
     if (layer == kOut) {
-      // sigma = fc_out row 0 . [h2, zs2] + b: the h2 part here, the code part from cn_code_bias
-      // (two packed chains: 32 v_pk_fma_f32 instead of one 64-deep fmaf chain)
-      typedef float float2v __attribute__((ext_vector_type(2)));
-      // the weights in two batches of 8 LDS reads issued together (one wait per batch; read one at
-      // a time, each FMA pair waited on its own read while both waves of the SIMD sat here)
-      float2v s0{0.0f, 0.0f}, s1{0.0f, 0.0f};
-      const floatx4* wsig = reinterpret_cast<const floatx4*>(clds + kCSig) + 16 * fresh(s.g);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        floatx4 w[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) w[k] = wsig[8 * h + k];
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int ob = 8 * h + k;
-          s0 = __builtin_elementwise_fma(float2v{w[k][0], w[k][1]}, float2v{s.act[ob][0], s.act[ob][1]}, s0);
-          s1 = __builtin_elementwise_fma(float2v{w[k][2], w[k][3]}, float2v{s.act[ob][2], s.act[ob][3]}, s1);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);
-      }
-      s.sig = (s0[0] + s0[1]) + (s1[0] + s1[1]);
+      s.sig = sigma_partial(s, clds);
     }
     if (layer == kXyz2) bias_code(s, a, crow_lds, kCbXyz2);
     else if (layer == kOut) bias_code(s, a, crow_lds, kCbFeat);
@@ -841,6 +856,178 @@ __global__ __launch_bounds__(kThreads, 2) void field_w16_kernel(FieldArgs a) {
   }
   // the last tile prefetched chunks 0..2 of a tile that does not exist: they must land
   // before the workgroup's LDS is released
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+}
+
+
+// ================================================================ density-only forward
+// sigma_raw alone (CodeNeRFModel.forward, model.py:174-186: layer_xyz1, layer_xyz2 with the shape
+// code, fc_out row 0): density is finished after the stream's first kSigmaChunks = 10 chunks, so
+// this kernel runs only those -- the field kernel's own building blocks in the field kernel's
+// order, hence its sigma bit for bit -- and neither decodes a view direction nor touches the
+// texture terms.  Chunk schedule per tile, running counter c (ring slot c & 3, source chunk
+// (c - s.cbase) mod 10; the counter is folded mod 20 = lcm(10, ring) between tiles):
+//   c+0, c+1   layer_xyz1   B = the xyz encodings (LazyXyz pairs in the first chunk's shadow, or
+//                            sincosf up front: decided per wave as in field_tile)
+//   c+2 .. c+9 layer_xyz2   B = relu(h1), accumulators from the code-bias row (kCbXyz2)
+//   epilogue                relu -> sigma_partial + the 4-group butterfly + code_bias[kCbSigma]
+// The last k-step of chunk c+9 pre-reads the next tile's first A fragments; the DMA issued in
+// chunks c+7 .. c+9 already fetches the next tile's chunks 0 .. 2.
+// LDS after the ring: the constants, then the layer_xyz2 code-bias vector (256 floats) per wave.
+constexpr int kSigLdsQuads = kRing * kChunkQuads + (kLdsConsts + kWaves * 256) / 4;
+static_assert(kSigLdsQuads * 16 <= 160 * 1024, "LDS budget (density)");
+static_assert((2 * kSigmaChunks) % kRing == 0, "the density counter folds mod 2 tiles");
+
+// The lazy encodings of layer_xyz1's first chunk without the view-direction work of LazyXyz's second.
+struct LazyXyzOnly {
+  const LazyXyz l;
+  static constexpr bool kLazy = true;
+  template <int T>
+  __device__ __forceinline__ float at() const { return l.template at<T>(); }
+  template <int T>
+  __device__ __forceinline__ void prep() const {
+    if constexpr (T + 1 < 8) l.template pair<T + 1>();
+  }
+};
+
+template <int MODE>
+__device__ __forceinline__ void sigma_tile(State& s, const DensityArgs& d, float4* lds, float* clds, float* crow_lds,
+                                          int64_t tile, int& c) {
+  const FieldArgs& a = d.f;
+  const int64_t row = tile * kTile + s.wave * 16 + (s.lane & 15);
+  const bool valid = row < a.m;
+  const int64_t rc = valid ? row : a.m - 1;
+  s.cbase = c;
+
+  // ---- the point (decode_sample's formulas), the code row and its layer_xyz2 / sigma terms
+  const int64_t ray = rc / a.n_samples;
+  float x[3] = {0.0f, 0.0f, 0.0f};
+  if constexpr (MODE == kFromPts) {
+    x[0] = a.pts[3 * rc]; x[1] = a.pts[3 * rc + 1]; x[2] = a.pts[3 * rc + 2];
+  } else if constexpr (MODE == kFromRayZ) {
+    const float zv = a.z[rc];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) x[j] = mul_add_rn(a.rd[3 * ray + j], zv, a.ro[3 * ray + j]);
+  }
+  s.crow = static_cast<int>(code_row(a, ray));
+  const int crow0 = __builtin_amdgcn_readfirstlane(s.crow);
+  s.uniform_code = __builtin_amdgcn_readfirstlane(__ballot(s.crow != crow0) == 0 ? 1 : 0) != 0;
+  float cbr[4];
+  {
+    const float* src = a.code_bias + (int64_t)crow0 * kCbStride + kCbXyz2;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cbr[k] = src[s.lane + 64 * k];
+  }
+  const float bs = a.code_bias[(int64_t)s.crow * kCbStride + kCbSigma];
+  float enc[16];
+  if constexpr (MODE == kFromEncoded) {
+    const float* xr = a.x + rc * d.x_stride;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int col = col_enc_xyz(t, s.g);
+      enc[t] = col >= 0 ? xr[col] : 0.0f;
+    }
+  }
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+#pragma unroll
+  for (int k = 0; k < 4; ++k) crow_lds[s.lane + 64 * k] = cbr[k];
+
+  // ---- encodings and layer_xyz1: as field_tile, the view direction's share of the range test
+  // dropped (a unit vector times at most 2^3 is always in range)
+  bool lazy = false;
+  if constexpr (MODE != kFromEncoded) {
+    const float xa = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fabsf(x[2])) * clds[kCFreq + 14];
+    const bool ok = xa <= kFastSinBound;  // false for NaN
+    lazy = __builtin_amdgcn_readfirstlane(__ballot(!ok) == 0 ? 1 : 0) != 0;
+  }
+  if (lazy) {
+    if constexpr (MODE != kFromEncoded) {
+      const int g = fresh(s.g);
+      float fr[11];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int p = 4 * i + g;
+        fr[i] = clds[kCFreq + ((p < 30 ? p : 0) * 11 >> 5)];  // (11 p) >> 5 = p / 3 for p < 32
+      }
+      fr[8] = fr[9] = fr[10] = 0.0f;  // the view direction's: not read
+      const LazyXyzOnly l0{LazyXyz{enc, s.denc, x, x, fr, g, false}};
+      l0.l.pair<0>();
+      bias_from(s, clds + kCB1);
+      chunk16<8, 0, kStreamSigma>(s, lds, c + 0, l0);
+      chunk16<8, 0, kStreamSigma>(s, lds, c + 1, ArrB<8>{enc});
+    }
+  } else {
+    if constexpr (MODE != kFromEncoded) {
+      const int g = fresh(s.g);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int p = 4 * i + g;
+        const int pc = p < 30 ? p : 0;
+        const float arg = __fmul_rn(pick3(x, pc % 3), clds[kCFreq + pc / 3]);
+        float sn, cs;
+        sincosf(arg, &sn, &cs);
+        if (i == 7 && p >= 30) {  // groups 2, 3: raw inputs
+          sn = s.g == 2 ? x[0] : x[2];
+          cs = s.g == 2 ? x[1] : 0.0f;
+        }
+        enc[i] = sn;
+        enc[8 + i] = cs;
+      }
+    }
+    bias_from(s, clds + kCB1);
+    chunk16<8, 0, kStreamSigma>(s, lds, c + 0, ArrB<0>{enc});
+    chunk16<8, 0, kStreamSigma>(s, lds, c + 1, ArrB<8>{enc});
+  }
+  c += 2;
+
+  // ---- layer_xyz2
+  relu_act<false>(s);
+  static_assert(kCbXyz2 == 0, "crow_lds holds the code-bias row's first 256 floats");
+  bias_code(s, a, crow_lds, kCbXyz2);
+  __builtin_amdgcn_sched_barrier(0);
+  layer256<kStreamSigma>(s, lds, c);
+
+  // ---- sigma
+  relu_act<false>(s);
+  float sg = sigma_partial(s, clds);
+  sg += __shfl_xor(sg, 16);
+  sg += __shfl_xor(sg, 32);
+  sg += bs;
+  if (valid && s.g == 0) {
+    if (d.sigma) d.sigma[row] = sg;
+    if (a.raw) reinterpret_cast<float4*>(a.raw)[row] = make_float4(0.0f, 0.0f, 0.0f, sg);
+  }
+  if (c >= 2 * kSigmaChunks) c -= 2 * kSigmaChunks;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kThreads, 2) void density_w16_kernel(DensityArgs d) {
+  // one LDS object, as field_w16_kernel
+  __shared__ __attribute__((aligned(16))) float4 lds[kSigLdsQuads];
+  float* clds = reinterpret_cast<float*>(lds + kRing * kChunkQuads);
+  State s;
+  s.lane = threadIdx.x & 63;
+  s.g = s.lane >> 4;
+  s.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  s.wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.f.packed), 0, kPackedFloats * 4, 0x00020000);
+  s.voff = static_cast<unsigned>(s.wave * 64 + s.lane) * 16u;
+  s.cbase = 0;
+  float* crow_lds = clds + kLdsConsts + s.wave * 256;
+
+  load_consts(d.f, clds);
+  dma_chunk<kStreamSigma>(s, lds, 0);
+  dma_chunk<kStreamSigma>(s, lds, 1);
+  dma_chunk<kStreamSigma>(s, lds, 2);
+  asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  read_a<0>(lds + s.lane, s.pre);
+
+  const int64_t n_tiles = (d.f.m + kTile - 1) / kTile;
+  int c = 0;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
+    sigma_tile<MODE>(s, d, lds, clds, crow_lds, tile, c);
+  // the last tile prefetched three chunks of a tile that does not exist: they must land before
+  // the workgroup's LDS is released
   __builtin_amdgcn_s_waitcnt(0x0F70);
 }
 
@@ -1555,6 +1742,17 @@ int launch_field_w16(int mode, FieldArgs& a, hipStream_t st) {
     case kFromPts: hipLaunchKernelGGL((w16::field_w16_kernel<kFromPts, false>), dim3(grid), b, 0, st, a); break;
     case kFromRayZ: hipLaunchKernelGGL((w16::field_w16_kernel<kFromRayZ, false>), dim3(grid), b, 0, st, a); break;
     default: hipLaunchKernelGGL((w16::field_w16_kernel<kFromEncoded, false>), dim3(grid), b, 0, st, a); break;
+  }
+  return cn::launch_status();
+}
+
+int launch_density_w16(int mode, DensityArgs& d, hipStream_t st) {
+  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(d.f.m, w16::kTile), cu_count_w16()));
+  const dim3 b(w16::kThreads);
+  switch (mode) {
+    case kFromPts: hipLaunchKernelGGL((w16::density_w16_kernel<kFromPts>), dim3(grid), b, 0, st, d); break;
+    case kFromRayZ: hipLaunchKernelGGL((w16::density_w16_kernel<kFromRayZ>), dim3(grid), b, 0, st, d); break;
+    default: hipLaunchKernelGGL((w16::density_w16_kernel<kFromEncoded>), dim3(grid), b, 0, st, d); break;
   }
   return cn::launch_status();
 }

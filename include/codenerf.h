@@ -245,6 +245,29 @@ int cn_radiance_field(const float* packed, int fmt, const float* code_bias, cons
                       const float* freqs_xyz, const float* freqs_dir, float* raw,
                       cn_stream_t stream);
 
+/* Density alone: sigma_raw of CodeNeRFModel.forward, model.py:174-186 (layer_xyz1, layer_xyz2 with
+ * the shape code, fc_out row 0) -- the first 10 of the field kernel's 36 weight chunks, 163,840 of
+ * its 572,416 FLOP per sample, and bit for bit the sigma_raw cn_radiance_field writes for the same
+ * point and code (finite view directions).  Neither a view direction nor the texture code enters:
+ * code_bias may be formed with any z_t.  fmt: CN_FMT_F32_W16 only (the other formats return
+ * CN_EUNSUPPORTED before any launch); packed is that format's cn_mlp_pack, unchanged.
+ * Exactly one input mode, m = n_rays * n_samples samples:
+ *   pts (m, 3);
+ *   ro, rd (n_rays, 3) and z (n_rays, n_samples): pts = ro + rd*z as cn_radiance_field forms them;
+ *   x: m pre-encoded rows, x_stride (>= 63) floats apart, of which the 63 xyz columns are read
+ *      ((m, 63) and (m, 90) rows both fit).
+ * code row of sample k = that of ray r = k / n_samples, as in cn_radiance_field: code_index[r], or
+ * row 0 (n_codes == 1), or row r (n_codes == n_rays).  freqs_xyz (10): a HOST array.
+ * Outputs, either or both: sigma (m); raw (m, 4) rows [0, 0, 0, sigma_raw], 16-byte aligned, which
+ * cn_volume_render and cn_sample_pdf take as they take a field's (their weights read sigma only).
+ * CN_EINVAL before any launch: packed, code_bias or freqs_xyz NULL; not exactly one mode (or a
+ * partial ro / rd / z); both outputs NULL; raw misaligned; a size <= 0; x_stride < 63; n_codes
+ * neither 1 nor n_rays without a code_index. */
+int cn_density_field(const float* packed, int fmt, const float* code_bias, const int64_t* code_index,
+                     int64_t n_codes, const float* pts, const float* ro, const float* rd, const float* z,
+                     const float* x, int64_t x_stride, int64_t n_rays, int64_t n_samples,
+                     const float* freqs_xyz, float* sigma, float* raw, cn_stream_t stream);
+
 /* --- Backward (autograd through the eval / train step) ------------------
  * The gradients loss.backward() takes through the path in the reference's
  * test-time optimisation (view_synthesis/eval.py) and training step:
