@@ -298,9 +298,13 @@ __global__ void pose_error_kernel(const float* __restrict__ gt, const float* __r
       g[4 * r + c] = static_cast<float>(acc);
     }
   // SO3.Log (lieutils.py:528-566)
-  const float tr = (g[0] + g[5]) + g[10];
+  // torch.trace's CPU kernel accumulates a float diagonal in double and rounds once; near t = pi one ulp of
+  // the trace moves t by ~1e3 ulp (d acos = -1 / sin t), so the sum is taken the same way
+  const float tr = static_cast<float>((static_cast<double>(g[0]) + static_cast<double>(g[5])) + static_cast<double>(g[10]));
   const float cth = (tr - 1.0f) / 2.0f;
-  const float t = acosf(cth);
+  // the correctly rounded acos (double, rounded once) rather than acosf's 1-2 ulp: at t = pi - 1e-3 one ulp
+  // of t changes sin t / t, and with it the twist, by 5e-4 relative
+  const float t = static_cast<float>(acos(static_cast<double>(cth)));
   const float sc = sin_by_t(t);
   float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f;
   if (fabsf(sc) > 1e-7f) {

@@ -133,8 +133,11 @@ __global__ __launch_bounds__(256) void ray_bundle_backward_kernel(const float* _
   if (threadIdx.x < 12) d_c2w[16 * b + threadIdx.x] += red[threadIdx.x][0];
 }
 
-// sample gather backward (ray_sampler.py:77-80): indices within an image are a
-// permutation prefix (unique), so the scatter is a plain store into zeroed grads.
+// sample gather backward (ray_sampler.py:77-80): a scatter-add.  The sampler's indices within
+// an image are a permutation prefix (unique), but the entry takes any index list (cn_pose_rays
+// does too), so two rays may select one pixel: the adds are float atomics.  A destination with a
+// single source gets one add onto its running value, bitwise the plain sum; out-of-range indices
+// (NaN rows in the forward) contribute nothing.
 __global__ void gather_rays_backward_kernel(const float* __restrict__ g_o, const float* __restrict__ g_d,
                                             int64_t batch, int64_t hw, const int64_t* __restrict__ sel, int64_t s,
                                             float* __restrict__ d_ro, float* __restrict__ d_rd) {
@@ -145,8 +148,8 @@ __global__ void gather_rays_backward_kernel(const float* __restrict__ g_o, const
     const int64_t dst = (b * hw + p) * 3;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      if (d_ro && g_o) d_ro[dst + j] += g_o[3 * q + j];
-      if (d_rd && g_d) d_rd[dst + j] += g_d[3 * q + j];
+      if (d_ro && g_o) atomicAdd(&d_ro[dst + j], g_o[3 * q + j]);
+      if (d_rd && g_d) atomicAdd(&d_rd[dst + j], g_d[3 * q + j]);
     }
   }
 }
