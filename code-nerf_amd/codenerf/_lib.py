@@ -19,8 +19,9 @@ LIB_PATH = os.environ.get("CODENERF_LIB", os.path.join(_HERE, "lib", "libcodener
 CN_OK, CN_EINVAL, CN_EUNSUPPORTED = 0, -1, -2
 CN_NUM_PARAMS = 18
 CN_FMT_F32, CN_FMT_BF16X3, CN_FMT_BF16X3_T, CN_FMT_F32_W16, CN_FMT_F32_W16_T, CN_FMT_BF16X3_W16 = 0, 1, 2, 3, 4, 5
+CN_FMT_F32_W16_FOLD = 6
 FORMATS = {"f32": CN_FMT_F32, "bf16x3": CN_FMT_BF16X3, "bf16x3_t": CN_FMT_BF16X3_T, "f32_w16": CN_FMT_F32_W16,
-           "f32_w16_t": CN_FMT_F32_W16_T, "bf16x3_w16": CN_FMT_BF16X3_W16}
+           "f32_w16_t": CN_FMT_F32_W16_T, "bf16x3_w16": CN_FMT_BF16X3_W16, "f32_w16_fold": CN_FMT_F32_W16_FOLD}
 
 
 def kernel_format(precision: str) -> str:
@@ -95,6 +96,9 @@ SIGNATURES = {
     "cn_mlp_packed_floats": (_i64, [_i]),
     "cn_mlp_pack": (_i, [ctypes.POINTER(_p), _i, _p, _p]),
     "cn_code_bias": (_i, [ctypes.POINTER(_p), _p, _p, _i64, _p, _p]),
+    "cn_fold_bias": (_i, [ctypes.POINTER(_p), _p, _i64, _p, _p]),
+    "cn_mlp_forward_fold": (_i, [_p, _i, _p, _p, _p, _i64, _p, _i64, _p, _p]),
+    "cn_radiance_field_fold": (_i, [_p, _i, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _fp, _fp, _p, _p]),
     "cn_field_prepare": (_i, [ctypes.POINTER(_p), _p, _p, _i64, _p, _p, _p, _p, _i64, _p]),
     "cn_field_prepare_models": (_i, [ctypes.POINTER(FieldPrep), _i, _p, _p, _i64, _p]),
     "cn_field_train_saved_floats": (_i64, [_i, _i64]),

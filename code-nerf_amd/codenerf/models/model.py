@@ -24,6 +24,25 @@ PARAM_ORDER = ("layer_xyz1", "layer_xyz2", "fc_out", "shape_code_layer1", "shape
                "texture_code_layer1", "layer_dir1", "layer_dir2", "fc_rgb")
 
 
+def fold_default() -> bool:
+    """Whether frozen-weight fp32 inference takes the folded kernel unless a model says otherwise."""
+    return os.environ.get("CODENERF_FOLD", "1") != "0"
+
+
+def inference_format(m) -> str:
+    """The packed format of ``m``'s no-grad forward (``m``: a CodeNeRFModel or torch_ops' parameter-list
+    model): its kernel_format(), or "f32_w16_fold" in place of "f32_w16" while ``m.fold`` is set."""
+    fmt = m.kernel_format()
+    return "f32_w16_fold" if fmt == "f32_w16" and m.fold else fmt
+
+
+def inference_pack(m, cb: torch.Tensor):
+    """-> (pack, format, fold_bias rows or None) of ``m``'s no-grad forward on code terms ``cb``."""
+    fmt = inference_format(m)
+    fold = ops.fold_bias(m.param_list(), cb) if fmt == "f32_w16_fold" else None
+    return m.packed(fmt), fmt, fold
+
+
 class CodeNeRFModel(torch.nn.Module):
     """model.py:123-194."""
 
@@ -52,8 +71,11 @@ class CodeNeRFModel(torch.nn.Module):
         # arithmetic of the training backward's weight-gradient / dX GEMMs, independent of the
         # inference format: the reference trains fully in fp32
         self.train_precision = os.environ.get("CODENERF_TRAIN_PRECISION", "f32")
-        self._packed = None
-        self._packed_key = None
+        # frozen-weight inference of precision "f32" runs the folded kernel ("f32_w16_fold": fc_out's
+        # feature rows folded into layer_dir1, 28 weight chunks per tile instead of 36); False (or
+        # CODENERF_FOLD=0 as the default) keeps the unfolded "f32_w16" kernel there too
+        self.fold = fold_default()
+        self._packs = {}          # format -> (weights' signature, pack)
 
     # --- kernel plumbing -------------------------------------------------
     def supported(self) -> bool:
@@ -79,16 +101,24 @@ class CodeNeRFModel(torch.nn.Module):
         from .._lib import kernel_format
         return kernel_format(self.precision)
 
-    def packed(self) -> torch.Tensor:
-        """MFMA-fragment layout of the weights, repacked whenever a parameter changed."""
+    def inference_format(self) -> str:
+        """The packed format of the no-grad forward: kernel_format(), or its folded form."""
+        return inference_format(self)
+
+    def packed(self, fmt: str = None) -> torch.Tensor:
+        """MFMA-fragment layout of the weights in ``fmt`` (default: kernel_format()), one cached pack per
+        format (density and forward alternate between two), each repacked whenever a parameter changed."""
         self._require_supported()
         params = self.param_list()
-        fmt = self.kernel_format()
-        key = (fmt,) + tuple((p.data_ptr(), p._version) for p in params)
-        if self._packed is None or self._packed_key != key:
-            self._packed = ops.mlp_pack(params, fmt)
-            self._packed_key = key
-        return self._packed
+        fmt = fmt or self.kernel_format()
+        sig = tuple((p.data_ptr(), p._version) for p in params)
+        hit = self._packs.get(fmt)
+        if hit is None or hit[0] != sig:
+            self._packs = {f: v for f, v in self._packs.items() if v[0] == sig}   # a parameter changed: all stale
+            hit = (sig, ops.mlp_pack(params, fmt))
+            self._packs[fmt] = hit
+        return hit[1]
+
 
     def code_bias(self, z_s: torch.Tensor, z_t: torch.Tensor) -> torch.Tensor:
         return ops.code_bias(self.param_list(), z_s, z_t)
@@ -109,7 +139,8 @@ class CodeNeRFModel(torch.nn.Module):
             return mlp_forward_autograd(self, z_s, z_t, x)
         codes_s, codes_t, index = _dedupe_codes(z_s, z_t)
         cb = ops.code_bias(self.param_list(), codes_s, codes_t)
-        return ops.mlp_forward(self.packed(), cb, x, index, precision=self.kernel_format())
+        packed, fmt, fold = inference_pack(self, cb)
+        return ops.mlp_forward(packed, cb, x, index, precision=fmt, fold_bias=fold)
 
 
     def density(self, z_s: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
@@ -153,8 +184,9 @@ def _field_op(m: CodeNeRFModel, cs, ct, rd, chunk_rows, fx, fd, pts=None, ro=Non
                                        code_index=code_index, pair=pair)
     cb = m.code_bias(cs, ct)
     n_samples = pts.shape[1] if pts is not None else z.shape[1]
-    return ops.radiance_field(m.packed(), cb, rd, n_samples, chunk_rows, fx, fd, pts=pts, ro=ro, z=z,
-                              code_index=code_index, precision=m.kernel_format())
+    packed, fmt, fold = inference_pack(m, cb)
+    return ops.radiance_field(packed, cb, rd, n_samples, chunk_rows, fx, fd, pts=pts, ro=ro, z=z,
+                              code_index=code_index, precision=fmt, fold_bias=fold)
 
 
 def _dedupe_codes(z_s: torch.Tensor, z_t: torch.Tensor):

@@ -285,7 +285,9 @@ def mlp_pack(params: Sequence[Tensor], precision: str = "f32") -> Tensor:
 
     precision "f32": fp32 fragments for v_mfma_f32_32x32x2_f32; "bf16x3": bf16 hi/lo
     fragments for the 3-product split on v_mfma_f32_32x32x16_bf16 (include/codenerf.h);
-    "bf16x3_t": the transposed 3xbf16 pack of the fused backward.
+    "bf16x3_t": the transposed 3xbf16 pack of the fused backward; "f32_w16_fold": the "f32_w16"
+    pack with fc_out's feature rows folded into layer_dir1 (frozen-weight inference; read by
+    mlp_forward / radiance_field together with fold_bias rows).
     """
     lib = _lib_ready()
     assert len(params) == _lib.CN_NUM_PARAMS, "expected the 18 CodeNeRFModel weight/bias tensors"
@@ -308,6 +310,31 @@ def code_bias(params: Sequence[Tensor], z_s: Tensor, z_t: Tensor) -> Tensor:
     check(lib.cn_code_bias(arr, ptr(z_s), ptr(z_t), z_s.shape[0], ptr(out), stream_of(out)), "cn_code_bias")
     del keep
     return out
+
+
+def fold_bias(params: Sequence[Tensor], cb: Tensor) -> Tensor:
+    """The folded layer's per-code bias (cn_fold_bias): W_dir1[:, :256] c_feat + b_dir1 for every row of
+    ``cb`` = code_bias(params, z_s, z_t), accumulated in double and rounded once -> (n_codes, 256)."""
+    lib = _lib_ready()
+    params = [_cuda(p.detach(), f"param{i}") for i, p in enumerate(params)]
+    cb = _cuda(cb, "cb")
+    assert cb.dim() == 2 and cb.shape[1] == _lib.CN_CODE_BIAS_STRIDE, "cb must be code_bias rows (n, 520)"
+    out = torch.empty(cb.shape[0], 256, device=cb.device, dtype=torch.float32)
+    arr, keep = _lib.pointer_array(params)
+    check(lib.cn_fold_bias(arr, ptr(cb), cb.shape[0], ptr(out), stream_of(out)), "cn_fold_bias")
+    del keep
+    return out
+
+
+def _fold_rows(precision: str, cb: Tensor, fold: Optional[Tensor]) -> Optional[Tensor]:
+    """The checked ``fold_bias`` argument of a forward: required by "f32_w16_fold", refused by the rest."""
+    if precision != "f32_w16_fold":
+        assert fold is None, f"fold_bias goes with precision 'f32_w16_fold', not {precision!r}"
+        return None
+    assert fold is not None, "precision 'f32_w16_fold' needs fold_bias = ops.fold_bias(params, cb)"
+    fold = _cuda(fold, "fold_bias")
+    assert fold.shape == (cb.shape[0], 256), "fold_bias must be (n_codes, 256)"
+    return fold
 
 
 def field_prepare(params: Sequence[Tensor], z_s: Tensor, z_t: Tensor, pack: bool = True, pack_t: bool = True,
@@ -379,9 +406,11 @@ def xenc_columns():
 
 
 def mlp_forward(packed: Tensor, cb: Tensor, x: Tensor, code_index: Optional[Tensor] = None,
-                precision: str = "f32") -> Tensor:
-    """CodeNeRFModel.forward on pre-encoded rows (model.py:160-194): (M, 90) -> (M, 4)."""
+                precision: str = "f32", fold_bias: Optional[Tensor] = None) -> Tensor:
+    """CodeNeRFModel.forward on pre-encoded rows (model.py:160-194): (M, 90) -> (M, 4).
+    precision "f32_w16_fold": ``packed`` that format's pack and ``fold_bias`` = ops.fold_bias(params, cb)."""
     lib = _lib_ready()
+    fold = _fold_rows(precision, cb, fold_bias)
     x = _cuda(x, "x")
     assert x.dim() == 2 and x.shape[1] == 90, "x must be (M, 63 + 27)"
     m = x.shape[0]
@@ -391,7 +420,10 @@ def mlp_forward(packed: Tensor, cb: Tensor, x: Tensor, code_index: Optional[Tens
     else:
         assert n_codes in (1, m), "codes must be one row or one row per sample"
     raw = torch.empty(m, 4, device=x.device, dtype=torch.float32)
-    if m:
+    if m and fold is not None:
+        check(lib.cn_mlp_forward_fold(ptr(packed), _fmt(precision), ptr(cb), ptr(fold), ptr(code_index), n_codes,
+                                      ptr(x), m, ptr(raw), stream_of(x)), "cn_mlp_forward_fold")
+    elif m:
         check(lib.cn_mlp_forward(ptr(packed), _fmt(precision), ptr(cb), ptr(code_index), n_codes, ptr(x), m, ptr(raw),
                                  stream_of(x)),
               "cn_mlp_forward")
@@ -401,9 +433,12 @@ def mlp_forward(packed: Tensor, cb: Tensor, x: Tensor, code_index: Optional[Tens
 def radiance_field(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int, chunk_rows: int,
                    freqs_xyz: Sequence[float], freqs_dir: Sequence[float], pts: Optional[Tensor] = None,
                    ro: Optional[Tensor] = None, z: Optional[Tensor] = None,
-                   code_index: Optional[Tensor] = None, precision: str = "f32") -> Tensor:
-    """forward_pass (nerf/__init__.py:94-134) fused with the MLP -> raw (R, S, 4)."""
+                   code_index: Optional[Tensor] = None, precision: str = "f32",
+                   fold_bias: Optional[Tensor] = None) -> Tensor:
+    """forward_pass (nerf/__init__.py:94-134) fused with the MLP -> raw (R, S, 4).
+    precision "f32_w16_fold": ``packed`` that format's pack and ``fold_bias`` = ops.fold_bias(params, cb)."""
     lib = _lib_ready()
+    fold = _fold_rows(precision, cb, fold_bias)
     rd = _cuda(rd, "rd")
     n = rd.shape[0]
     if pts is not None:
@@ -419,7 +454,12 @@ def radiance_field(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int, chunk
         assert n_codes in (1, n), "codes must be one row or one row per ray"
     assert len(freqs_xyz) == 10 and len(freqs_dir) == 4, "the field kernel implements L_xyz=10, L_dir=4"
     raw = torch.empty(n, n_samples, 4, device=rd.device, dtype=torch.float32)
-    if n:
+    if n and fold is not None:
+        check(lib.cn_radiance_field_fold(ptr(packed), _fmt(precision), ptr(cb), ptr(fold), ptr(code_index), n_codes,
+                                         ptr(pts), ptr(ro), ptr(rd), ptr(z), n, n_samples, chunk_rows,
+                                         _lib.host_floats(freqs_xyz), _lib.host_floats(freqs_dir), ptr(raw),
+                                         stream_of(rd)), "cn_radiance_field_fold")
+    elif n:
         check(lib.cn_radiance_field(ptr(packed), _fmt(precision), ptr(cb), ptr(code_index), n_codes, ptr(pts), ptr(ro),
                                     ptr(rd), ptr(z), n, n_samples, chunk_rows, _lib.host_floats(freqs_xyz),
                                     _lib.host_floats(freqs_dir), ptr(raw), stream_of(rd)), "cn_radiance_field")

@@ -264,7 +264,9 @@ class _ParamModel:
     """The model interface codenerf.nerf's field dispatch needs, over a bare parameter list."""
 
     def __init__(self, params, precision):
+        from .models.model import fold_default
         self._params, self.precision = list(params), precision
+        self.fold = fold_default()     # the module's default: the op and the module run the same kernel
 
     def param_list(self):
         return self._params
@@ -272,8 +274,8 @@ class _ParamModel:
     def kernel_format(self):
         return _lib.kernel_format(self.precision)
 
-    def packed(self):
-        return ops.mlp_pack(self._params, self.kernel_format())
+    def packed(self, fmt=None):
+        return ops.mlp_pack(self._params, fmt or self.kernel_format())
 
     def code_bias(self, z_s, z_t):
         return ops.code_bias(self._params, z_s, z_t)

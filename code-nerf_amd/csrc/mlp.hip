@@ -375,7 +375,9 @@ int launch_field(int fmt, int mode, FieldArgs& a, hipStream_t st) {
 bool valid_fmt(int fmt) {
   return fmt == CN_FMT_F32 || fmt == CN_FMT_BF16X3 || fmt == CN_FMT_F32_W16 || fmt == CN_FMT_BF16X3_W16;
 }
-bool valid_pack_fmt(int fmt) { return valid_fmt(fmt) || fmt == CN_FMT_BF16X3_T || fmt == CN_FMT_F32_W16_T; }
+bool valid_pack_fmt(int fmt) {
+  return valid_fmt(fmt) || fmt == CN_FMT_BF16X3_T || fmt == CN_FMT_F32_W16_T || fmt == CN_FMT_F32_W16_FOLD;
+}
 
 }  // namespace
 
@@ -385,6 +387,7 @@ static_assert(kCbStride == CN_CODE_BIAS_STRIDE, "code-bias stride mismatch");
 extern "C" int64_t cn_mlp_packed_floats(int fmt) {
   if (!valid_pack_fmt(fmt)) return -1;
   if (fmt == CN_FMT_F32_W16 || fmt == CN_FMT_F32_W16_T) return packed_floats_w16();
+  if (fmt == CN_FMT_F32_W16_FOLD) return packed_floats_w16_fold();
   if (fmt == CN_FMT_BF16X3_W16) return packed_floats_x3w();
   return fmt == CN_FMT_F32 ? kPackedFloats : packed_floats_x3();
 }
@@ -396,6 +399,7 @@ extern "C" int cn_mlp_pack(const float* const* params, int fmt, float* packed, c
   if (fmt == CN_FMT_BF16X3_T) return launch_pack_x3t(P, packed, cn::as_stream(stream));
   if (fmt == CN_FMT_F32_W16) return launch_pack_w16(P, packed, cn::as_stream(stream));
   if (fmt == CN_FMT_F32_W16_T) return launch_pack_w16t(P, packed, cn::as_stream(stream));
+  if (fmt == CN_FMT_F32_W16_FOLD) return launch_pack_w16_fold(P, packed, cn::as_stream(stream));
   if (fmt == CN_FMT_BF16X3_W16) return launch_pack_x3w(P, packed, cn::as_stream(stream));
   hipLaunchKernelGGL(pack_kernel, dim3(cn::elementwise_grid(kPackedFloats, 256)), dim3(256), 0,
                      cn::as_stream(stream), P, packed);
@@ -410,6 +414,14 @@ extern "C" int cn_code_bias(const float* const* params, const float* z_s, const 
   hipLaunchKernelGGL(code_bias_kernel, dim3(static_cast<unsigned>(n_codes * kCbSlices)), dim3(kCbThreads), 0,
                      cn::as_stream(stream), P, z_s, z_t, code_bias);
   return cn::launch_status();
+}
+
+extern "C" int cn_fold_bias(const float* const* params, const float* code_bias, int64_t n_codes, float* fold_bias,
+                            cn_stream_t stream) {
+  Params P;
+  if (make_params(params, &P) != CN_OK) return CN_EINVAL;
+  CN_CHECK_ARG(code_bias && fold_bias && n_codes > 0 && n_codes * kFbSlices <= (1ll << 31) - 1);
+  return launch_fold_bias(P, code_bias, n_codes, fold_bias, cn::as_stream(stream));
 }
 
 extern "C" int cn_field_prepare(const float* const* params, const float* z_s, const float* z_t, int64_t n_codes,
@@ -439,36 +451,57 @@ extern "C" int cn_field_prepare_models(const cn_field_prep* models, int n_models
   return launch_field_prepare_w16(pm, n_models, z_s, z_t, n_codes, cn::as_stream(stream));
 }
 
-extern "C" int cn_mlp_forward(const float* packed, int fmt, const float* code_bias,
-                              const int64_t* code_index, int64_t n_codes, const float* x,
-                              int64_t m, float* raw, cn_stream_t stream) {
-  CN_CHECK_ARG(packed && code_bias && x && raw && m > 0 && n_codes > 0 && valid_fmt(fmt));
+namespace {
+
+// fmt at a forward entry point: the folded pack runs through the *_fold entry points only, and they
+// take no other (CN_EUNSUPPORTED, before any other check and without a launch).
+int forward_fmt_status(int fmt, bool fold_entry) {
+  if (!(valid_fmt(fmt) || fmt == CN_FMT_F32_W16_FOLD)) return CN_EINVAL;
+  return (fmt == CN_FMT_F32_W16_FOLD) == fold_entry ? CN_OK : CN_EUNSUPPORTED;
+}
+
+int launch_field_any(int fmt, int mode, FieldArgs& a, hipStream_t st) {
+  return fmt == CN_FMT_F32_W16_FOLD ? launch_field_w16_fold(mode, a, st) : launch_field(fmt, mode, a, st);
+}
+
+// cn_mlp_forward / cn_mlp_forward_fold (fold_entry: fold_bias required)
+int mlp_forward_any(const float* packed, int fmt, bool fold_entry, const float* code_bias, const float* fold_bias,
+                    const int64_t* code_index, int64_t n_codes, const float* x, int64_t m, float* raw,
+                    cn_stream_t stream) {
+  const int rc = forward_fmt_status(fmt, fold_entry);
+  if (rc != CN_OK) return rc;
+  CN_CHECK_ARG(packed && code_bias && x && raw && m > 0 && n_codes > 0 && (!fold_entry || fold_bias));
   CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == m);
   CN_CHECK_ARG(cn::ceil_div(m, kTile) <= 0x7fffffff);
   FieldArgs a = {};
   a.packed = packed;
   a.code_bias = code_bias;
+  a.fold_bias = fold_bias;
   a.code_index = code_index;
   a.n_codes = n_codes;
   a.x = x;
   a.m = m;
   a.raw = raw;
   CN_CHECK_ARG(cn::aligned16(raw));  // float4 rows (include/codenerf.h)
-  return launch_field(fmt, kFromEncoded, a, cn::as_stream(stream));
+  CN_CHECK_ARG(cn::aligned16(fold_bias));  // 16-B vector reads of a c_v1 row
+  return launch_field_any(fmt, kFromEncoded, a, cn::as_stream(stream));
 }
 
-extern "C" int cn_radiance_field(const float* packed, int fmt, const float* code_bias,
-                                 const int64_t* code_index, int64_t n_codes, const float* pts,
-                                 const float* ro, const float* rd, const float* z, int64_t n_rays,
-                                 int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz,
-                                 const float* freqs_dir, float* raw, cn_stream_t stream) {
-  CN_CHECK_ARG(packed && code_bias && rd && raw && freqs_xyz && freqs_dir && valid_fmt(fmt));
+// cn_radiance_field / cn_radiance_field_fold
+int radiance_field_any(const float* packed, int fmt, bool fold_entry, const float* code_bias, const float* fold_bias,
+                       const int64_t* code_index, int64_t n_codes, const float* pts, const float* ro,
+                       const float* rd, const float* z, int64_t n_rays, int64_t n_samples, int64_t chunk_rows,
+                       const float* freqs_xyz, const float* freqs_dir, float* raw, cn_stream_t stream) {
+  const int rc = forward_fmt_status(fmt, fold_entry);
+  if (rc != CN_OK) return rc;
+  CN_CHECK_ARG(packed && code_bias && rd && raw && freqs_xyz && freqs_dir && (!fold_entry || fold_bias));
   CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && chunk_rows > 0 && n_codes > 0);
   CN_CHECK_ARG(pts || (ro && z));
   CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == n_rays);
   FieldArgs a = {};
   a.packed = packed;
   a.code_bias = code_bias;
+  a.fold_bias = fold_bias;
   a.code_index = code_index;
   a.n_codes = n_codes;
   a.pts = pts;
@@ -484,7 +517,40 @@ extern "C" int cn_radiance_field(const float* packed, int fmt, const float* code
   for (int i = 0; i < 4; ++i) a.fd[i] = freqs_dir[i];
   a.raw = raw;
   CN_CHECK_ARG(cn::aligned16(raw));  // float4 rows (include/codenerf.h)
-  return launch_field(fmt, pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream));
+  CN_CHECK_ARG(cn::aligned16(fold_bias));  // 16-B vector reads of a c_v1 row
+  return launch_field_any(fmt, pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream));
+}
+
+}  // namespace
+
+extern "C" int cn_mlp_forward(const float* packed, int fmt, const float* code_bias,
+                              const int64_t* code_index, int64_t n_codes, const float* x,
+                              int64_t m, float* raw, cn_stream_t stream) {
+  return mlp_forward_any(packed, fmt, false, code_bias, nullptr, code_index, n_codes, x, m, raw, stream);
+}
+
+extern "C" int cn_mlp_forward_fold(const float* packed, int fmt, const float* code_bias, const float* fold_bias,
+                                   const int64_t* code_index, int64_t n_codes, const float* x, int64_t m,
+                                   float* raw, cn_stream_t stream) {
+  return mlp_forward_any(packed, fmt, true, code_bias, fold_bias, code_index, n_codes, x, m, raw, stream);
+}
+
+extern "C" int cn_radiance_field(const float* packed, int fmt, const float* code_bias,
+                                 const int64_t* code_index, int64_t n_codes, const float* pts,
+                                 const float* ro, const float* rd, const float* z, int64_t n_rays,
+                                 int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz,
+                                 const float* freqs_dir, float* raw, cn_stream_t stream) {
+  return radiance_field_any(packed, fmt, false, code_bias, nullptr, code_index, n_codes, pts, ro, rd, z, n_rays,
+                            n_samples, chunk_rows, freqs_xyz, freqs_dir, raw, stream);
+}
+
+extern "C" int cn_radiance_field_fold(const float* packed, int fmt, const float* code_bias, const float* fold_bias,
+                                      const int64_t* code_index, int64_t n_codes, const float* pts,
+                                      const float* ro, const float* rd, const float* z, int64_t n_rays,
+                                      int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz,
+                                      const float* freqs_dir, float* raw, cn_stream_t stream) {
+  return radiance_field_any(packed, fmt, true, code_bias, fold_bias, code_index, n_codes, pts, ro, rd, z, n_rays,
+                            n_samples, chunk_rows, freqs_xyz, freqs_dir, raw, stream);
 }
 
 extern "C" int cn_density_field(const float* packed, int fmt, const float* code_bias, const int64_t* code_index,
@@ -501,7 +567,7 @@ extern "C" int cn_density_field(const float* packed, int fmt, const float* code_
   CN_CHECK_ARG(n_rays <= INT64_MAX / n_samples && cn::ceil_div(n_rays * n_samples, kTile) <= 0x7fffffff);
   CN_CHECK_ARG(!x || x_stride >= kDimXyz);
   CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == n_rays);
-  if (fmt != CN_FMT_F32_W16) return valid_fmt(fmt) ? CN_EUNSUPPORTED : CN_EINVAL;
+  if (fmt != CN_FMT_F32_W16) return (valid_fmt(fmt) || fmt == CN_FMT_F32_W16_FOLD) ? CN_EUNSUPPORTED : CN_EINVAL;
   DensityArgs d = {};
   d.f.packed = packed;
   d.f.code_bias = code_bias;

@@ -53,6 +53,8 @@ struct FieldArgs {
   float* ray_part;       // (m / wave samples, 6): each wave's d ro, d rd of its ray (the points' part)
   float* q1_part;        // (m, 3): each sample's d rd of its Q1 view-direction ray
   int64_t n_blocks;      // set by the backward launchers: the grid they launched
+  // folded fp32 inference forward (CN_FMT_F32_W16_FOLD): (n_codes, 256) c_v1 rows of cn_fold_bias
+  const float* fold_bias;
 };
 
 // The density-only forward (cn_density_field): the field's inputs (f.raw optional here; f.x rows
@@ -304,6 +306,13 @@ int launch_pack_w16(const Params& P, float* packed, hipStream_t st);
 int launch_field_w16(int mode, FieldArgs& a, hipStream_t st);  // a.masks: also the ReLU masks
 int launch_density_w16(int mode, DensityArgs& d, hipStream_t st);  // sigma only: the stream's first 10 chunks
 int64_t mask_words_w16(int64_t m);
+// the folded inference form (fc_out's feature rows folded into layer_dir1): its pack, the per-code
+// c_v1 rows and the forward on them (a.fold_bias; no masks, no planes)
+constexpr int kFbSlices = 4;  // fold_bias workgroups per code row
+int64_t packed_floats_w16_fold();
+int launch_pack_w16_fold(const Params& P, float* packed, hipStream_t st);
+int launch_fold_bias(const Params& P, const float* code_bias, int64_t n_codes, float* fold_bias, hipStream_t st);
+int launch_field_w16_fold(int mode, FieldArgs& a, hipStream_t st);
 int launch_pack_w16t(const Params& P, float* packed, hipStream_t st);
 // code_bias + the CN_FMT_F32_W16 / _T packs + a zeroed buffer (any of them null: skipped), for one or
 // two models on the same codes, in one launch

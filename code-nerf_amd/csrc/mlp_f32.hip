@@ -106,59 +106,128 @@ __host__ __device__ constexpr int col_enc_dir(int s, int g) {
 
 // ---------------------------------------------------------------- packing
 
+// Element `rem` of chunk c of the CN_FMT_F32_W16 stream.
+__device__ __forceinline__ float pack_w16_stream_elem(const Params& P, int c, int rem) {
+  float v = 0.0f;
+  if (c == kCRgb) {
+    // fc_rgb: 64 k-steps of block 0, [k-step quad][lane][k-step & 3] (the former MFMA form,
+    // not read any more; the chunk keeps its size and place in the stream), then at kRgbValu
+    // rows 0..2 over v2 for the VALU form,
+    // [row][g][ob][r] = W_rgb[row][16 ob + 4 g + r]
+    if (rem < 64 * 64) {
+      const int lane = (rem % 256) / 4, t = 4 * (rem / 256) + rem % 4;
+      const int i = lane & 15, g = lane >> 4;
+      if (i < 3) v = P.p[kWRgb][i * (kHidden + kCode) + col_acc(t, g)];
+    } else if (rem >= kRgbValu && rem < kRgbValu + 3 * 256) {
+      const int t = rem - kRgbValu, i = t >> 8, g = (t >> 6) & 3, ob = (t >> 2) & 15, r = t & 3;
+      v = P.p[kWRgb][i * (kHidden + kCode) + 16 * ob + 4 * g + r];
+    }
+  } else {
+    const int s = rem / (kStepQuads * 4), q = (rem % (kStepQuads * 4)) / 256;
+    const int lane = (rem % 256) / 4, ob = 4 * q + rem % 4;
+    const int i = lane & 15, g = lane >> 4;
+    int row = 16 * ob + i, col = -1, in_dim = 0;
+    const float* W = nullptr;
+    if (c < kCL2) { W = P.p[kWXyz1]; in_dim = kDimXyz; col = col_enc_xyz(8 * c + s, g); }
+    else if (c < kCL3) { W = P.p[kWXyz2]; in_dim = kHidden + kCode; col = col_acc(8 * (c - kCL2) + s, g); }
+    else if (c < kCL4) { W = P.p[kWOut]; in_dim = kHidden + kCode; row += 1; col = col_acc(8 * (c - kCL3) + s, g); }
+    else if (c < kCDir) { W = P.p[kWDir1]; in_dim = kCode + kDimDir; col = col_acc(8 * (c - kCL4) + s, g); }
+    else if (c == kCDir) {
+      W = P.p[kWDir1]; in_dim = kCode + kDimDir;
+      const int e = col_enc_dir(s, g);
+      col = e < 0 ? -1 : kCode + e;
+    } else { W = P.p[kWDir2]; in_dim = kHidden; col = col_acc(8 * (c - kCL5) + s, g); }
+    if (col >= 0) v = W[row * in_dim + col];
+  }
+  return v;
+}
+
+// Constant j of the pack's tail (kConsts): b_xyz1 | b_dir1 | b_dir2 | sigma weights.
+__device__ __forceinline__ float pack_w16_const(const Params& P, int j) {
+  if (j < 256) return P.p[kBXyz1][j];
+  if (j < 512) return P.p[kBDir1][j - 256];
+  if (j < 768) return P.p[kBDir2][j - 512];
+  const int t = j - kCSig, g = t >> 6, ob = (t >> 2) & 15, r = t & 3;
+  return P.p[kWOut][16 * ob + 4 * g + r];  // fc_out row 0, input feature 16 ob + 4 g + r of h2
+}
+
 // Elements idx0, idx0 + stride, ... of the CN_FMT_F32_W16 pack (pack_w16_kernel; a role of
 // field_prepare_kernel).
 __device__ __forceinline__ void pack_w16_range(const Params& P, float* __restrict__ packed, int idx0, int stride) {
-  for (int idx = idx0; idx < kPackedFloats; idx += stride) {
-    float v = 0.0f;
-    if (idx >= kStreamFloats) {
-      const int j = idx - kStreamFloats;
-      if (j < 256) v = P.p[kBXyz1][j];
-      else if (j < 512) v = P.p[kBDir1][j - 256];
-      else if (j < 768) v = P.p[kBDir2][j - 512];
-      else {
-        const int t = j - kCSig, g = t >> 6, ob = (t >> 2) & 15, r = t & 3;
-        v = P.p[kWOut][16 * ob + 4 * g + r];  // fc_out row 0, input feature 16 ob + 4 g + r of h2
-      }
+  for (int idx = idx0; idx < kPackedFloats; idx += stride)
+    packed[idx] = idx >= kStreamFloats ? pack_w16_const(P, idx - kStreamFloats)
+                                       : pack_w16_stream_elem(P, idx / (kChunkQuads * 4), idx % (kChunkQuads * 4));
+}
+
+__global__ void pack_w16_kernel(Params P, float* __restrict__ packed) {
+  pack_w16_range(P, packed, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
+// The folded inference pack (CN_FMT_F32_W16_FOLD).  fc_out's 256 feature rows feed layer_dir1 with
+// no activation between them (model.py:186-189), so with frozen weights the two layers are one:
+//   v1_pre = W_f relu(h2) + W_dir1[:, 256:] enc(view) + c_v1[code]
+//   W_f = W_dir1[:, :256] W_out[1:, :256]                     (here, once per weight version)
+//   c_v1[code] = W_dir1[:, :256] c_feat[code] + b_dir1        (fold_bias_kernel, per code row)
+// The stream is the CN_FMT_F32_W16 one with fc_out's and layer_dir1's 16 chunks replaced by W_f's 8
+// (same fragment layout and column maps): xyz1 2 | xyz2 8 | fold 8 | view-dir 1 | dir2 8 | rgb 1.
+// The constants keep their places (the LDS copy is the unfolded kernel's); b_dir1's slot is zero,
+// b_dir1 lives in c_v1.
+constexpr int kFFold = kCL3, kFDir = 18, kFoldChunks = 28;  // dir2 from 19, rgb 27
+constexpr int kFoldStreamFloats = kFoldChunks * kChunkQuads * 4;
+constexpr int kFoldPackedFloats = kFoldStreamFloats + kConsts;
+static_assert(kFoldChunks % kRing == 0, "cyclic stream: chunk c + 28 reuses chunk c's ring slot");
+
+__global__ void pack_w16_fold_kernel(Params P, float* __restrict__ packed) {
+  constexpr int kX2 = kHidden + kCode, kD1 = kCode + kDimDir;
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < kFoldPackedFloats; idx += gridDim.x * blockDim.x) {
+    float v;
+    if (idx >= kFoldStreamFloats) {
+      const int j = idx - kFoldStreamFloats;
+      v = (j >= kCBD1 && j < kCBD2) ? 0.0f : pack_w16_const(P, j);
     } else {
       const int c = idx / (kChunkQuads * 4), rem = idx % (kChunkQuads * 4);
-      if (c == kCRgb) {
-        // fc_rgb: 64 k-steps of block 0, [k-step quad][lane][k-step & 3] (the former MFMA form,
-        // not read any more; the chunk keeps its size and place in the stream), then at kRgbValu
-        // rows 0..2 over v2 for the VALU form,
-        // [row][g][ob][r] = W_rgb[row][16 ob + 4 g + r]
-        if (rem < 64 * 64) {
-          const int lane = (rem % 256) / 4, t = 4 * (rem / 256) + rem % 4;
-          const int i = lane & 15, g = lane >> 4;
-          if (i < 3) v = P.p[kWRgb][i * (kHidden + kCode) + col_acc(t, g)];
-        } else if (rem >= kRgbValu && rem < kRgbValu + 3 * 256) {
-          const int t = rem - kRgbValu, i = t >> 8, g = (t >> 6) & 3, ob = (t >> 2) & 15, r = t & 3;
-          v = P.p[kWRgb][i * (kHidden + kCode) + 16 * ob + 4 * g + r];
-        }
-      } else {
+      if (c >= kFFold && c < kFDir) {
+        // W_f[row][col]: a 256-term dot product in double (each product exact), rounded once
         const int s = rem / (kStepQuads * 4), q = (rem % (kStepQuads * 4)) / 256;
         const int lane = (rem % 256) / 4, ob = 4 * q + rem % 4;
-        const int i = lane & 15, g = lane >> 4;
-        int row = 16 * ob + i, col = -1, in_dim = 0;
-        const float* W = nullptr;
-        if (c < kCL2) { W = P.p[kWXyz1]; in_dim = kDimXyz; col = col_enc_xyz(8 * c + s, g); }
-        else if (c < kCL3) { W = P.p[kWXyz2]; in_dim = kHidden + kCode; col = col_acc(8 * (c - kCL2) + s, g); }
-        else if (c < kCL4) { W = P.p[kWOut]; in_dim = kHidden + kCode; row += 1; col = col_acc(8 * (c - kCL3) + s, g); }
-        else if (c < kCDir) { W = P.p[kWDir1]; in_dim = kCode + kDimDir; col = col_acc(8 * (c - kCL4) + s, g); }
-        else if (c == kCDir) {
-          W = P.p[kWDir1]; in_dim = kCode + kDimDir;
-          const int e = col_enc_dir(s, g);
-          col = e < 0 ? -1 : kCode + e;
-        } else { W = P.p[kWDir2]; in_dim = kHidden; col = col_acc(8 * (c - kCL5) + s, g); }
-        if (col >= 0) v = W[row * in_dim + col];
+        const int row = 16 * ob + (lane & 15), col = col_acc(8 * (c - kFFold) + s, lane >> 4);
+        const float* wd = P.p[kWDir1] + row * kD1;
+        const float* wo = P.p[kWOut] + kX2 + col;
+        double acc = 0.0;
+        for (int k = 0; k < kCode; ++k) acc += static_cast<double>(wd[k]) * static_cast<double>(wo[k * kX2]);
+        v = static_cast<float>(acc);
+      } else {
+        // the unfolded stream's chunk with the same contents
+        v = pack_w16_stream_elem(P, c < kFFold ? c : c + (kCDir - kFDir), rem);
       }
     }
     packed[idx] = v;
   }
 }
 
-__global__ void pack_w16_kernel(Params P, float* __restrict__ packed) {
-  pack_w16_range(P, packed, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+// c_v1 (n_codes, 256) = W_dir1[:, :256] c_feat[code] + b_dir1, c_feat the kCbFeat slot of the code's
+// cn_code_bias row: kFbSlices workgroups per code row, one wave-wide dot product per output
+// (double partial sums and butterfly, rounded once).
+constexpr int kFbThreads = 256;
+__global__ __launch_bounds__(kFbThreads) void fold_bias_kernel(Params P, const float* __restrict__ code_bias,
+                                                               float* __restrict__ out) {
+  constexpr int kRows = kHidden / kFbSlices, kW = kFbThreads / 64;
+  const int64_t code = blockIdx.x / kFbSlices;
+  const int q = blockIdx.x % kFbSlices, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* cf = code_bias + code * kCbStride + kCbFeat;
+  double cv[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) cv[j] = cf[lane + 64 * j];
+  for (int r = wave; r < kRows; r += kW) {
+    const int row = kRows * q + r;
+    const float* w = P.p[kWDir1] + row * (kCode + kDimDir);
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s += static_cast<double>(w[lane + 64 * j]) * cv[j];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) out[code * kHidden + row] = static_cast<float>(s + static_cast<double>(P.p[kBDir1][row]));
+  }
 }
 
 // ---------------------------------------------------------------- kernel state
@@ -181,8 +250,8 @@ struct State {
 };
 
 // The kernel's LDS constants (after the ring): the packed ones and the encoding frequencies.
-__device__ __forceinline__ void load_consts(const FieldArgs& a, float* clds) {
-  for (int k = threadIdx.x; k < kConsts; k += kThreads) clds[k] = a.packed[kStreamFloats + k];
+__device__ __forceinline__ void load_consts(const FieldArgs& a, float* clds, int stream_floats = kStreamFloats) {
+  for (int k = threadIdx.x; k < kConsts; k += kThreads) clds[k] = a.packed[stream_floats + k];
   if (threadIdx.x < 16) {
     const int t = threadIdx.x;
     float mx = 0.0f, md = 0.0f;  // the largest |frequency| of each encoding (fast_sincosf's range check)
@@ -243,13 +312,15 @@ __device__ __forceinline__ int stream_src_sigma(const State& s, int cn) {
   return k >= kSigmaChunks ? k - kSigmaChunks : k;
 }
 // Which stream a chunk counter walks (dma_piece): a bool NOGEO converts to the first two.
-constexpr int kStreamFull = 0, kStreamNG = 1, kStreamSigma = 2;
+// kStreamFold: the folded pack's kFoldChunks chunks from cn = 0 in every tile, as kStreamFull.
+constexpr int kStreamFull = 0, kStreamNG = 1, kStreamSigma = 2, kStreamFold = 3;
 
 // One LDS-DMA piece: 1 KiB of chunk cn (piece p of 4 for this wave).
 template <int NG = kStreamFull>
 __device__ __forceinline__ void dma_piece(const State& s, float4* lds, int cn, int p) {
   const int src = NG == kStreamSigma ? stream_src_sigma(s, cn)
                   : NG == kStreamNG  ? stream_src_ng(s, cn)
+                  : NG == kStreamFold ? (cn < kFoldChunks ? cn : cn - kFoldChunks)
                                      : (cn < kChunks ? cn : cn - kChunks);
   const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(src * kChunkQuads + p * 64 * kWaves) * 16u);
   __builtin_amdgcn_raw_ptr_buffer_load_lds(
@@ -487,6 +558,18 @@ __device__ __forceinline__ void bias_code(State& s, const FieldArgs& a, const fl
   }
 }
 
+// The folded kernel's c_v1 row of this lane's code: the wave's LDS copy (staged where c_feat sits
+// in the unfolded kernel's row), or a per-lane global read, as bias_code.
+static_assert(kCbFeat == 256 && kCbSigma == kCbFeat + 256, "c_v1 is staged in c_feat's 256 floats of crow_lds");
+__device__ __forceinline__ void bias_fold(State& s, const FieldArgs& a, const float* crow_lds) {
+  if (s.uniform_code) {
+    bias_from(s, crow_lds + kCbFeat);
+  } else {
+    bias_from(s, a.fold_bias + (int64_t)s.crow * kHidden);
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+  }
+}
+
 // ReLU masks for the fused backward: 4 layers (h1, h2, v1, v2) x 64 bits per lane (bit 4 ob + r
 // of feature 16 ob + 4 g + r: pre-activation > 0), one 8-B store per lane per layer.
 constexpr int kMaskLayers = 4;
@@ -608,9 +691,15 @@ __device__ __forceinline__ float sigma_partial(const State& s, const float* clds
 // (5, m, 256) planes, feature 16 ob + 4 g + r: one 16-B store per block per lane).
 
 
-template <int MODE, bool MASKS, bool SAVE = false>
+// FOLD (inference only: no masks, no planes): the CN_FMT_F32_W16_FOLD stream.  After relu(h2) and
+// sigma_partial -- chunks 0..9 and that epilogue are the unfolded kernel's, so sigma has its bits --
+// the accumulators start from the code's c_v1 row and take W_f's 8 chunks over relu(h2) and the
+// view-direction chunk: layer_dir1's pre-activation without fc_out's 8 chunks before it.
+template <int MODE, bool MASKS, bool SAVE = false, bool FOLD = false>
 __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4* lds, float* clds, float* crow_lds,
                                           int64_t tile, int& c) {
+  static_assert(!FOLD || (!MASKS && !SAVE), "the folded kernel has no feat plane and no fc_out input gradient");
+  constexpr int NG = FOLD ? kStreamFold : kStreamFull;
   const int64_t row = tile * kTile + s.wave * 16 + (s.lane & 15);
   const bool valid = row < a.m;
   const int64_t rc = valid ? row : a.m - 1;
@@ -626,7 +715,8 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
       const int j = s.lane + 64 * k;
-      cbr[k] = j < kCbStride ? src[j] : 0.0f;
+      if (FOLD && k >= kCbFeat / 64 && k < kCbSigma / 64) cbr[k] = a.fold_bias[(int64_t)crow0 * kHidden + j - kCbFeat];
+      else cbr[k] = j < kCbStride ? src[j] : 0.0f;
     }
   }
   float enc[16];
@@ -676,11 +766,11 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
       const LazyXyz l0{enc, s.denc, in.x, in.vd, fr, g, false};
       l0.pair<0>();
       bias_from(s, clds + kCB1);
-      chunk16<8>(s, lds, c + 0, l0);
+      chunk16<8, 0, NG>(s, lds, c + 0, l0);
       if constexpr (SAVE)
-        chunk16<8, 0>(s, lds, c + 1, LazyXyz{enc, s.denc, in.x, in.vd, fr, g, true}, XencStore{s, a, tile, enc});
+        chunk16<8, 0, NG>(s, lds, c + 1, LazyXyz{enc, s.denc, in.x, in.vd, fr, g, true}, XencStore{s, a, tile, enc});
       else
-        chunk16<8>(s, lds, c + 1, LazyXyz{enc, s.denc, in.x, in.vd, fr, g, true});
+        chunk16<8, 0, NG>(s, lds, c + 1, LazyXyz{enc, s.denc, in.x, in.vd, fr, g, true});
     }
   } else {
     if constexpr (MODE != kFromEncoded) {
@@ -709,20 +799,23 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
     }
     s.denc[7] = 0.0f;
     bias_from(s, clds + kCB1);
-    chunk16<8>(s, lds, c + 0, ArrB<0>{enc});
+    chunk16<8, 0, NG>(s, lds, c + 0, ArrB<0>{enc});
     if constexpr (SAVE)
-      chunk16<8, 0>(s, lds, c + 1, ArrB<8>{enc}, XencStore{s, a, tile, enc});
+      chunk16<8, 0, NG>(s, lds, c + 1, ArrB<8>{enc}, XencStore{s, a, tile, enc});
     else
-      chunk16<8>(s, lds, c + 1, ArrB<8>{enc});
+      chunk16<8, 0, NG>(s, lds, c + 1, ArrB<8>{enc});
   }
   c += 2;
 
   // ---- layer_xyz2, fc_out, layer_dir1 (+ view-dir chunk), layer_dir2
+  // (FOLD: the kOut turn runs the folded layer -- c_v1, W_f's chunks, the view-dir chunk -- and
+  // there is no kDir1 turn)
   for (int layer = kXyz2; layer <= kDir2; ++layer) {
+    if (FOLD && layer == kDir1) continue;
     // activation of the previous layer's outputs: ReLU, none after fc_out (feat); its mask words
     // and its plane (h1, h2, feat, v1) are stored at this layer's first chunk barrier
     uint2v mw = uint2v{0u, 0u};
-    if (layer == kDir1) {
+    if (!FOLD && layer == kDir1) {
 #pragma unroll
       for (int ob = 0; ob < 16; ++ob) s.act[ob] = s.acc[ob];
     } else {
@@ -734,12 +827,13 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
       s.sig = sigma_partial(s, clds);
     }
     if (layer == kXyz2) bias_code(s, a, crow_lds, kCbXyz2);
+    else if (FOLD && layer == kOut) bias_fold(s, a, crow_lds);
     else if (layer == kOut) bias_code(s, a, crow_lds, kCbFeat);
     else bias_from(s, clds + (layer == kDir1 ? kCBD1 : kCBD2));
     __builtin_amdgcn_sched_barrier(0);
-    layer256(s, lds, c, st);
-    if (layer == kDir1) {
-      chunk16<7>(s, lds, c, ArrB<0>{s.denc});
+    layer256<NG>(s, lds, c, st);
+    if (layer == (FOLD ? kOut : kDir1)) {
+      chunk16<7, 0, NG>(s, lds, c, ArrB<0>{s.denc});
       c += 1;
     }
   }
@@ -797,7 +891,7 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
     };
     blocks(std::integral_constant<int, 0>{});
     chunk_barrier();
-    dma_chunk(s, lds, c + 3);
+    dma_chunk<NG>(s, lds, c + 3);
     st_v2.template blocks<0, 8>();
     blocks(std::integral_constant<int, 8>{});
     st_v2.template blocks<8, 8>();
@@ -823,7 +917,7 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
 }
 
 
-template <int MODE, bool MASKS, bool SAVE = false>
+template <int MODE, bool MASKS, bool SAVE = false, bool FOLD = false>
 __global__ __launch_bounds__(kThreads, 2) void field_w16_kernel(FieldArgs a) {
   // ONE LDS object (a second one makes hipcc wait vmcnt(0) before ring reads): the DMA
   // ring, then the constants, then one code-bias row per wave
@@ -833,17 +927,19 @@ __global__ __launch_bounds__(kThreads, 2) void field_w16_kernel(FieldArgs a) {
   s.lane = threadIdx.x & 63;
   s.g = s.lane >> 4;
   s.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  s.wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.packed), 0, kPackedFloats * 4, 0x00020000);
+  constexpr int NG = FOLD ? kStreamFold : kStreamFull;
+  s.wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.packed), 0,
+                                             (FOLD ? kFoldPackedFloats : kPackedFloats) * 4, 0x00020000);
   s.voff = static_cast<unsigned>(s.wave * 64 + s.lane) * 16u;
   s.poff = static_cast<unsigned>(s.wave * 16 + (s.lane & 15)) * 1024u + 16u * s.g;
   s.sig = 0.0f;
   float* crow_lds = clds + kLdsConsts + s.wave * kCbStride;
 
-  load_consts(a, clds);
+  load_consts(a, clds, FOLD ? kFoldStreamFloats : kStreamFloats);
   // prime the ring with chunks 0..2, wait for chunk 0 everywhere, read its first fragments
-  dma_chunk(s, lds, 0);
-  dma_chunk(s, lds, 1);
-  dma_chunk(s, lds, 2);
+  dma_chunk<NG>(s, lds, 0);
+  dma_chunk<NG>(s, lds, 1);
+  dma_chunk<NG>(s, lds, 2);
   asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
   read_a<0>(lds + s.lane, s.pre);
@@ -852,7 +948,7 @@ __global__ __launch_bounds__(kThreads, 2) void field_w16_kernel(FieldArgs a) {
   int c = 0;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     c = 0;
-    field_tile<MODE, MASKS, SAVE>(s, a, lds, clds, crow_lds, tile, c);
+    field_tile<MODE, MASKS, SAVE, FOLD>(s, a, lds, clds, crow_lds, tile, c);
   }
   // the last tile prefetched chunks 0..2 of a tile that does not exist: they must land
   // before the workgroup's LDS is released
@@ -1742,6 +1838,32 @@ int launch_field_w16(int mode, FieldArgs& a, hipStream_t st) {
     case kFromPts: hipLaunchKernelGGL((w16::field_w16_kernel<kFromPts, false>), dim3(grid), b, 0, st, a); break;
     case kFromRayZ: hipLaunchKernelGGL((w16::field_w16_kernel<kFromRayZ, false>), dim3(grid), b, 0, st, a); break;
     default: hipLaunchKernelGGL((w16::field_w16_kernel<kFromEncoded, false>), dim3(grid), b, 0, st, a); break;
+  }
+  return cn::launch_status();
+}
+
+int64_t packed_floats_w16_fold() { return w16::kFoldPackedFloats; }
+
+int launch_pack_w16_fold(const Params& P, float* packed, hipStream_t st) {
+  hipLaunchKernelGGL(w16::pack_w16_fold_kernel, dim3(cn::elementwise_grid(w16::kFoldPackedFloats, 256)), dim3(256), 0,
+                     st, P, packed);
+  return cn::launch_status();
+}
+
+int launch_fold_bias(const Params& P, const float* code_bias, int64_t n_codes, float* fold_bias, hipStream_t st) {
+  hipLaunchKernelGGL(w16::fold_bias_kernel, dim3(static_cast<unsigned>(n_codes * kFbSlices)),
+                     dim3(w16::kFbThreads), 0, st, P, code_bias, fold_bias);
+  return cn::launch_status();
+}
+
+int launch_field_w16_fold(int mode, FieldArgs& a, hipStream_t st) {
+  if (!a.fold_bias || a.masks || a.save) return CN_EINVAL;
+  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(a.m, w16::kTile), cu_count_w16()));
+  const dim3 b(w16::kThreads);
+  switch (mode) {
+    case kFromPts: hipLaunchKernelGGL((w16::field_w16_kernel<kFromPts, false, false, true>), dim3(grid), b, 0, st, a); break;
+    case kFromRayZ: hipLaunchKernelGGL((w16::field_w16_kernel<kFromRayZ, false, false, true>), dim3(grid), b, 0, st, a); break;
+    default: hipLaunchKernelGGL((w16::field_w16_kernel<kFromEncoded, false, false, true>), dim3(grid), b, 0, st, a); break;
   }
   return cn::launch_status();
 }

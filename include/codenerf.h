@@ -65,6 +65,16 @@ typedef void* cn_stream_t; /* hipStream_t */
  *                    cn_mlp_forward / cn_radiance_field only -- the mask-writing forward and
  *                    the fused backward take CN_FMT_BF16X3 / _T). */
 #define CN_FMT_BF16X3_W16 5
+/*   CN_FMT_F32_W16_FOLD the CN_FMT_F32_W16 pack for inference with frozen weights, with fc_out's 256
+ *                    feature rows folded into layer_dir1 (model.py:186-189 has no activation between
+ *                    them): W_f = W_dir1[:, :256] W_out[1:, :256], each element a 256-term dot product
+ *                    accumulated in double and rounded once.  28 weight chunks per tile instead of
+ *                    36 (xyz1 2 | xyz2 8 | fold 8 | view-dir 1 | dir2 8 | rgb 1), 441,344 instead of
+ *                    572,416 FLOP per sample; sigma_raw has CN_FMT_F32_W16's bits.  Read by
+ *                    cn_mlp_forward_fold / cn_radiance_field_fold only, with cn_fold_bias's rows; every
+ *                    other entry point returns CN_EUNSUPPORTED for it.  No training or backward form
+ *                    (their gradients need feat and fc_out's input gradient). */
+#define CN_FMT_F32_W16_FOLD 6
 
 const char* cn_version(void);
 const char* cn_error_string(int code);
@@ -198,6 +208,13 @@ int cn_mlp_pack(const float* const* params, int fmt, float* packed, cn_stream_t 
 int cn_code_bias(const float* const* params, const float* z_s, const float* z_t,
                  int64_t n_codes, float* code_bias, cn_stream_t stream);
 
+/* The per-code bias of the folded layer (CN_FMT_F32_W16_FOLD): fold_bias row i =
+ * W_dir1[:, :256] c_feat[i] + b_dir1, c_feat the second 256 floats of code_bias row i (cn_code_bias),
+ * accumulated in double and rounded once.  code_bias: (n_codes, CN_CODE_BIAS_STRIDE); fold_bias:
+ * (n_codes, 256).  One small launch. */
+int cn_fold_bias(const float* const* params, const float* code_bias, int64_t n_codes, float* fold_bias,
+                 cn_stream_t stream);
+
 /* Everything a step needs from a model's weights and codes before its fp32 field kernels, in ONE
  * launch (what the reference recomputes inside every CodeNeRFModel.forward, model.py:160-194):
  * code_bias as cn_code_bias (NULL: skipped), packed / packed_t as cn_mlp_pack with CN_FMT_F32_W16
@@ -244,6 +261,21 @@ int cn_radiance_field(const float* packed, int fmt, const float* code_bias, cons
                       const float* z, int64_t n_rays, int64_t n_samples, int64_t chunk_rows,
                       const float* freqs_xyz, const float* freqs_dir, float* raw,
                       cn_stream_t stream);
+
+/* cn_mlp_forward / cn_radiance_field on a CN_FMT_F32_W16_FOLD pack: the same arguments plus
+ * fold_bias (n_codes, 256), cn_fold_bias of the same code_bias rows.  raw's sigma_raw is bit for bit
+ * the unfolded CN_FMT_F32_W16 kernel's; rgb_raw differs from it by the rounding of W_f and c_v1
+ * (and is exact wherever the unfolded kernel is, i.e. while every partial sum is an integer below
+ * 2^24).  Any other fmt returns CN_EUNSUPPORTED, as cn_mlp_forward / cn_radiance_field do for
+ * CN_FMT_F32_W16_FOLD, before any other check and without a launch. */
+int cn_mlp_forward_fold(const float* packed, int fmt, const float* code_bias, const float* fold_bias,
+                        const int64_t* code_index, int64_t n_codes, const float* x, int64_t m, float* raw,
+                        cn_stream_t stream);
+int cn_radiance_field_fold(const float* packed, int fmt, const float* code_bias, const float* fold_bias,
+                           const int64_t* code_index, int64_t n_codes, const float* pts, const float* ro,
+                           const float* rd, const float* z, int64_t n_rays, int64_t n_samples,
+                           int64_t chunk_rows, const float* freqs_xyz, const float* freqs_dir, float* raw,
+                           cn_stream_t stream);
 
 /* Density alone: sigma_raw of CodeNeRFModel.forward, model.py:174-186 (layer_xyz1, layer_xyz2 with
  * the shape code, fc_out row 0) -- the first 10 of the field kernel's 36 weight chunks, 163,840 of
