@@ -33,6 +33,7 @@ def kernel_format(precision: str) -> str:
         return "f32"
     return precision
 CN_CODE_BIAS_STRIDE = 520
+CN_EMPTY_SIGMA_RAW = -1.0e4     # sigma_raw of a culled slot (cn_occupancy_expand): exactly zero density
 
 _p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -105,6 +106,10 @@ SIGNATURES = {
     "cn_mlp_forward": (_i, [_p, _i, _p, _p, _i64, _p, _i64, _p, _p]),
     "cn_radiance_field": (_i, [_p, _i, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _fp, _fp, _p, _p]),
     "cn_density_field": (_i, [_p, _i, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _fp, _p, _p, _p]),
+    "cn_occupancy_build": (_i, [_p, _i64, _f, _i, _p, _p]),
+    "cn_occupancy_cull_workspace_bytes": (_i64, [_i64, _i64]),
+    "cn_occupancy_cull": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _f, _f, _p, _p, _p, _p, _p, _p, _p]),
+    "cn_occupancy_expand": (_i, [_p, _p, _i64, _i64, _p, _p]),
     "cn_radiance_field_train": (_i, [_p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _fp, _fp, _p, _p, _p]),
     "cn_mlp_forward_train": (_i, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p]),
     "cn_encode_inputs": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _fp, _fp, _p, _p]),

@@ -25,7 +25,7 @@ from .volumetric_render import volume_render
 
 __all__ = ["RaySampler", "PointSampler", "PositionalEmbedder", "volume_render", "prepare_samplers",
            "prepare_embedders", "predict_radiance_and_render", "forward_pass", "parallel_image_render",
-           "render_rays", "gather_rows", "gather_views", "density", "density_grid"]
+           "render_rays", "gather_rows", "gather_views", "density", "density_grid", "OccupancyGrid"]
 
 
 def prepare_samplers(cfg, height: int, width: int, intrinsics, datatype, device) -> Tuple[RaySampler, PointSampler]:
@@ -166,6 +166,75 @@ def density_grid(model, embedders, z_s: torch.Tensor, resolution: int, bound: fl
     return out.view(d, d, d)
 
 
+class OccupancyGrid:
+    """One shape code's occupancy bits for sample culling in the inference render (render_rays'
+    ``occupancy``): the cube [-bound, bound]^3 in ``resolution``^3 cells (a multiple of 32 in
+    [32, 512]), one bit per cell in ``bits``, a device int32 tensor of resolution^3 / 32 words -- cell
+    (ix, iy, iz) is bit c & 31 of word c >> 5, c = (ix G + iy) G + iz (include/codenerf.h).  A sample
+    in an empty cell, or outside the cube, skips the field and counts as exactly zero density."""
+
+    def __init__(self, bits: torch.Tensor, resolution: int, bound: float):
+        g = int(resolution)
+        if not (g % 32 == 0 and 32 <= g <= 512):
+            raise ValueError(f"resolution must be a multiple of 32 in [32, 512], got {resolution}")
+        if not float(bound) > 0.0:
+            raise ValueError(f"bound must be positive, got {bound}")
+        if bits.dtype != torch.int32 or bits.dim() != 1 or bits.numel() != g * g * g // 32:
+            raise ValueError(f"bits must be {g * g * g // 32} int32 words, got {tuple(bits.shape)} {bits.dtype}")
+        self.bits, self.resolution, self.bound = bits.contiguous(), g, float(bound)
+
+    @classmethod
+    def full(cls, resolution: int, bound: float, device) -> "OccupancyGrid":
+        """Every cell occupied: culls only the samples outside the cube."""
+        g = int(resolution)
+        return cls(torch.full((g * g * g // 32,), -1, dtype=torch.int32, device=device), g, bound)
+
+    @classmethod
+    def from_nodes(cls, nodes: torch.Tensor, threshold: float, dilate: int = 1, *, bound: float) -> "OccupancyGrid":
+        """From node densities (G+1, G+1, G+1) at linspace(-bound, bound, G+1) per axis (what
+        density_grid(resolution=G + 1) returns): ops.occupancy_build."""
+        return cls(ops.occupancy_build(nodes, threshold, dilate), nodes.shape[0] - 1, bound)
+
+    @classmethod
+    def from_density(cls, model, embedders, z_s: torch.Tensor, resolution: int = 128, *, bound: float,
+                     threshold: float, dilate: int = 1) -> "OccupancyGrid":
+        """From ``model``'s activated density of shape code ``z_s`` (1, 256): density_grid(resolution + 1,
+        activated=True), then from_nodes.  ``threshold`` (in activated density) has no default."""
+        nodes = density_grid(model, embedders, z_s, int(resolution) + 1, bound, activated=True)
+        return cls.from_nodes(nodes, threshold, dilate, bound=bound)
+
+    def occupied_fraction(self) -> float:
+        """Share of the cells that are occupied (reads the bits back: a host synchronisation)."""
+        b = self.bits.view(torch.uint8)
+        set_bits = sum(int(((b >> k) & 1).sum()) for k in range(8))
+        return set_bits / float(self.resolution ** 3)
+
+
+def _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy: OccupancyGrid, density_only: bool):
+    """A render field call under an occupancy grid: cull -> ``model``'s inference field in points mode
+    over the M' kept samples (the density kernel when ``density_only``) -> expand to raw (R, S, 4).
+    Kept samples get the bits of the unculled call; culled ones the zero-density row."""
+    from ..models.model import _field_op, density_code_bias
+    fx, fd = _check_embedders(embedders)
+    cs, ct, code_index = _codes(z_s, z_t)
+    m = _unwrap(model)
+    with torch.no_grad():
+        many = cs.shape[0] > 1
+        count, _, pts, vdir, code_out, state = ops.occupancy_cull(
+            ro.detach(), rd.detach(), z, chunk_rows, occupancy.bits, occupancy.resolution, occupancy.bound,
+            code_index=code_index, want_code=many)
+        raw = None
+        if count:
+            index = code_out if many else None
+            if density_only:
+                raw = ops.density_field(m.packed(), density_code_bias(m, cs), fx, pts=pts, code_index=index,
+                                        want_sigma=False, want_raw=True)
+            else:
+                raw = _field_op(m, cs.detach(), ct.detach(), vdir, count, fx, fd, pts=pts.view(count, 1, 3),
+                                code_index=index)
+        return ops.occupancy_expand(raw, state)
+
+
 def forward_pass(model, embedders, rd: torch.Tensor, pts: torch.Tensor,
                  object_embedding: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
     """nerf/__init__.py:94-134: embed + MLP for one chunk -> (R, S, 4).
@@ -182,7 +251,7 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
                 point_sampler: PointSampler, embedders, coarse_model, fine_model=None, chunk_rows: Optional[int] = None,
                 t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
                 coarse_only: bool = False, events: Optional[dict] = None,
-                coarse_rgb: bool = True) -> Dict[str, torch.Tensor]:
+                coarse_rgb: bool = True, occupancy: Optional[OccupancyGrid] = None) -> Dict[str, torch.Tensor]:
     """predict_radiance_and_render over a whole ray list, chunk semantics kept via ``chunk_rows``.
 
     Returns rgb/depth/acc for the coarse pass (+ weights) and, unless
@@ -194,12 +263,20 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     resampling, which read densities alone, so the coarse field runs the density kernel (raw rows
     [0, 0, 0, sigma_raw], the same sigma bits) and the result has no "rgb_coarse"; everything else
     in it is bitwise the default call's.
+    ``occupancy`` (inference only): an OccupancyGrid of the rendered object.  Each field call then
+    culls its samples against the grid, runs the field over the kept ones alone and expands the result;
+    a culled sample has exactly zero density (not the reference's softplus tail), a kept one the
+    unculled call's bits.  The kept count is read back on the host once per field call, so this
+    render is not graph-capturable.
     """
-    if not coarse_rgb:
+    if not coarse_rgb or occupancy is not None:
         if torch.is_grad_enabled() and (
                 any(t is not None and t.requires_grad for t in (ro, rd, z_s, z_t)) or
                 any(p.requires_grad for m in (coarse_model, fine_model) if m is not None
                     for p in _unwrap(m).param_list())):
+            if coarse_rgb:
+                raise ValueError("occupancy culling is an inference render: the compacted field has no backward "
+                                 "(render under torch.no_grad(), or pass occupancy=None)")
             raise ValueError("coarse_rgb=False is the inference render: the density kernel has no backward "
                              "(render under torch.no_grad(), or keep coarse_rgb=True)")
 
@@ -221,7 +298,15 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     _, z_c = ops.sample_uniform(ro.detach(), rd.detach(), ps.z_vals, ps.lower, ps.upper,
                                 t_rand if ps.perturb else None, want_pts=False)
     pair = None
-    if fine_model is not None and not coarse_only and coarse_rgb:
+    if occupancy is not None:
+        def culled(density_only):
+            def field(model, embedders, rd, z_s, z_t, chunk_rows, ro=None, z=None, pair=None):
+                return _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy, density_only)
+            return field
+        coarse_field, fine_field = culled(not coarse_rgb), culled(False)
+    else:
+        coarse_field, fine_field = (_field if coarse_rgb else _density_field_raw), _field
+    if fine_model is not None and not coarse_only and coarse_rgb and occupancy is None:
         # the two differentiable fields' pre-field launches (code terms, packs, zeroed accumulators) as
         # one launch; each field takes its part (no launch when either runs without gradients)
         from ..autograd import new_field_pair, prefetch_render_prepares
@@ -234,7 +319,7 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     # pts = ro + rd z is formed inside the field kernel (z detached, point_sampler.py:115); with
     # gradients on, the field's backward returns d ro / d rd through both the points and the view dirs
     raw_c = timed_field(coarse_model, embedders, rd, z_s, z_t, chunk_rows, ro=ro, z=z_c, pair=pair,
-                        field=_field if coarse_rgb else _density_field_raw)
+                        field=coarse_field)
     rgb_c, disp_c, acc_c, w_c, depth_c = volume_render(raw_c, z_c, rd)
     out = {"rgb_coarse": rgb_c, "disp_coarse": disp_c, "acc_coarse": acc_c, "weights_coarse": w_c,
            "depth_coarse": depth_c, "z_coarse": z_c}
@@ -246,7 +331,7 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
         u = torch.rand(n, ps.num_samples_fine, dtype=torch.float32, device=ro.device)
     _, z_f = ops.sample_pdf(ro.detach(), rd.detach(), w_c.detach()[..., 1:-1], z_c, ps.num_samples_fine,
                             u if ps.perturb else ps.u_lin, want_pts=False)
-    raw_f = timed_field(fine_model, embedders, rd, z_s, z_t, chunk_rows, ro=ro, z=z_f, pair=pair)
+    raw_f = timed_field(fine_model, embedders, rd, z_s, z_t, chunk_rows, ro=ro, z=z_f, pair=pair, field=fine_field)
     rgb_f, disp_f, acc_f, _, depth_f = volume_render(raw_f, z_f, rd)
     out.update({"rgb_fine": rgb_f, "disp_fine": disp_f, "acc_fine": acc_f, "depth_fine": depth_f, "z_fine": z_f})
     return out
@@ -264,7 +349,7 @@ def predict_radiance_and_render(rays: Tuple[torch.Tensor, torch.Tensor], point_s
 
 def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, samplers, embedders, device,
                           key: str = "rgb_fine", coarse_only: bool = False,
-                          coarse_rgb: bool = True) -> Optional[torch.Tensor]:
+                          coarse_rgb: bool = True, occupancy: Optional[OccupancyGrid] = None) -> Optional[torch.Tensor]:
     """nerf/__init__.py:137-226: shard the image's rays over ranks, render, gather on rank 0.
 
     The split is the reference's (Q5: truncating, the last rank takes the
@@ -273,7 +358,7 @@ def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, sam
     semantics; one all-gather (RCCL over xGMI on MI355X) of the padded
     per-rank rows.  Rank 0 returns (H*W, 3); the others return None.
     ``coarse_rgb=False``: the coarse pass computes densities only (render_rays); ``key`` cannot then
-    be "rgb_coarse".
+    be "rgb_coarse".  ``occupancy``: an OccupancyGrid of the object, for render_rays' sample culling.
     """
     if not coarse_rgb and key == "rgb_coarse":
         raise ValueError('coarse_rgb=False renders no coarse colours: key="rgb_coarse" needs coarse_rgb=True')
@@ -297,7 +382,7 @@ def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, sam
         z_t = z_t.to(device).expand(num_rays, -1)[sl]
         out = render_rays(ro[sl].to(device), rd[sl].to(device), z_s, z_t, point_sampler, embedders,
                           models["nerf_coarse"], models.get("nerf_fine"), cfg.nerf.validation.chunksize,
-                          coarse_only=coarse_only, coarse_rgb=coarse_rgb)
+                          coarse_only=coarse_only, coarse_rgb=coarse_rgb, occupancy=occupancy)
         rgb = out[key]
         if not is_distributed:
             return rgb

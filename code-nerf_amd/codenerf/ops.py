@@ -518,6 +518,96 @@ def density_field(packed: Tensor, cb: Tensor, freqs_xyz: Sequence[float], *, pts
     return sigma if want_sigma else raw
 
 
+# ------------------------------------------------------------------ occupancy-grid culling
+
+
+def _grid_scale(resolution: int, bound: float) -> Tuple[float, float]:
+    """(lo, inv_cell) of the point lookup (include/codenerf.h): -bound and G / (2 bound), which the
+    ctypes call rounds to fp32."""
+    return -float(bound), resolution / (2.0 * float(bound))
+
+
+def occupancy_build(nodes: Tensor, threshold: float, dilate: int = 1) -> Tensor:
+    """Occupancy bits from node densities (cn_occupancy_build): ``nodes`` (G+1, G+1, G+1), axis order
+    [ix, iy, iz] -- what nerf.density_grid(resolution=G + 1) returns -> int32 words (G^3 / 32,).  A cell
+    is occupied iff a node within ``dilate`` (0..2) cells of it is > ``threshold`` or NaN."""
+    lib = _lib_ready()
+    nodes = _cuda(nodes, "nodes")
+    assert nodes.dim() == 3 and nodes.shape[0] == nodes.shape[1] == nodes.shape[2], "nodes must be (G+1, G+1, G+1)"
+    g = nodes.shape[0] - 1
+    assert g % 32 == 0 and 32 <= g <= 512, "the grid resolution G must be a multiple of 32 in [32, 512]"
+    assert dilate in (0, 1, 2), "dilate must be 0, 1 or 2"
+    bits = torch.empty(g * g * g // 32, device=nodes.device, dtype=torch.int32)
+    check(lib.cn_occupancy_build(ptr(nodes), g, float(threshold), int(dilate), ptr(bits), stream_of(nodes)),
+          "cn_occupancy_build")
+    return bits
+
+
+def occupancy_cull(ro: Tensor, rd: Tensor, z: Tensor, chunk_rows: int, bits: Tensor, resolution: int, bound: float,
+                   code_index: Optional[Tensor] = None, want_code: bool = True):
+    """Test every ray sample against an occupancy grid and compact the occupied ones
+    (cn_occupancy_cull) -> (count, sample_index (M',) int32, pts (M', 3), vdir (M', 3), code_out (M',)
+    int64 or None, state), M' = ``count`` samples in ascending sample order.  ``vdir`` holds the
+    unnormalised rd row of each sample's Q1 view-direction ray and ``code_out`` its code row
+    (``code_index[r]``, or r): with rd=vdir, n_samples=1, chunk_rows=M' the rows are a points-mode
+    input of radiance_field / density_field.  ``state`` goes to occupancy_expand.
+
+    This is the one place that reads ``count`` back (``.item()``): a HOST SYNCHRONISATION, since the
+    field launch over the compact rows is sized by it.  A culled render is therefore not
+    graph-capturable, although the C ABI entries themselves are stream-ordered and are."""
+    lib = _lib_ready()
+    ro, rd, z = _cuda(ro, "ro"), _cuda(rd, "rd"), _cuda(z, "z_vals")
+    bits = _cuda(bits, "bits", torch.int32)
+    assert z.dim() == 2, "z must be (num_rays, num_samples)"
+    n, s = z.shape
+    assert ro.shape == (n, 3) and rd.shape == (n, 3), "ro / rd must be (num_rays, 3)"
+    g = int(resolution)
+    assert g % 32 == 0 and 32 <= g <= 512 and bits.shape == (g * g * g // 32,), \
+        "bits must be the (G^3 / 32,) words of a grid of resolution G, a multiple of 32 in [32, 512]"
+    if code_index is not None:
+        code_index = _cuda(code_index, "code_index", torch.int64)
+        assert code_index.shape == (n,), "code_index must be (num_rays,)"
+    dev = z.device
+    m = n * s
+    sample_index = torch.empty(m, device=dev, dtype=torch.int32)
+    pts = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    vdir = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    code_out = torch.empty(m, device=dev, dtype=torch.int64) if want_code else None
+    if m == 0:
+        return 0, sample_index, pts, vdir, code_out, (None, n, s, 0)
+    ws_bytes = lib.cn_occupancy_cull_workspace_bytes(n, s)
+    if ws_bytes < 0:
+        raise ValueError(f"occupancy_cull: {n} rays x {s} samples is outside 1..512 samples / 2^31 - 1 rows")
+    workspace = torch.empty((ws_bytes + 7) // 8, device=dev, dtype=torch.int64)
+    count = torch.empty(1, device=dev, dtype=torch.int64)
+    lo, inv_cell = _grid_scale(g, bound)
+    check(lib.cn_occupancy_cull(ptr(ro), ptr(rd), ptr(z), n, s, int(chunk_rows), ptr(code_index), ptr(bits), g, lo,
+                                inv_cell, ptr(workspace), ptr(count), ptr(sample_index), ptr(pts), ptr(vdir),
+                                ptr(code_out), stream_of(z)), "cn_occupancy_cull")
+    k = int(count.item())       # host synchronisation (see the docstring)
+    return (k, sample_index[:k], pts[:k], vdir[:k], None if code_out is None else code_out[:k],
+            (workspace, n, s, k))
+
+
+def occupancy_expand(raw_compact: Optional[Tensor], state) -> Tensor:
+    """The compact field result (M', 4) back at its samples (cn_occupancy_expand) -> raw (R, S, 4);
+    culled slots hold [0, 0, 0, CN_EMPTY_SIGMA_RAW]: exactly zero density.  ``state``: occupancy_cull's;
+    ``raw_compact`` may be None when that call kept nothing."""
+    lib = _lib_ready()
+    workspace, n, s, k = state
+    if raw_compact is not None:
+        raw_compact = _aligned16(_cuda(raw_compact, "raw_compact").reshape(-1, 4))
+        assert raw_compact.shape[0] == k, f"raw_compact must hold the {k} kept rows"
+    else:
+        assert k == 0, f"raw_compact is required: {k} samples were kept"
+    dev = workspace.device if workspace is not None else torch.device("cuda")
+    raw = torch.empty(n, s, 4, device=dev, dtype=torch.float32)
+    if n * s:
+        check(lib.cn_occupancy_expand(ptr(raw_compact), ptr(workspace), n, s, ptr(raw), stream_of(raw)),
+              "cn_occupancy_expand")
+    return raw
+
+
 # ------------------------------------------------------------------ backward (A14)
 
 

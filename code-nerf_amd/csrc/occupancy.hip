@@ -1,0 +1,269 @@
+// Occupancy-grid sample culling for the inference render.
+//
+// A grid is G^3 cells over the cube [-bound, bound]^3, one bit per cell: cell (ix, iy, iz) is bit
+// c & 31 of 32-bit word c >> 5, c = (ix G + iy) G + iz.  Three passes around the unchanged field
+// kernels:
+//   build   node densities -> the bit words (a wave's ballot is two words);
+//   cull    every ray sample looked up; the kept ones compacted, in ascending sample order, into
+//           (point, Q1 view-direction row, code row) triples -- a points-mode input of the field
+//           kernels with n_samples = 1 -- and the kept masks / ray offsets left in a workspace;
+//   expand  the compact (M', 4) result gathered back to (R, S, 4), culled slots the empty row.
+// All three are bandwidth / latency bound: one wave per ray, ballots and mbcnt ranks, no atomics, so
+// the compact order (and with it every output) is deterministic.
+#include <limits.h>
+
+#include "cn_common.h"
+
+namespace {
+
+constexpr int kMaxSamples = 512;           // as cn_volume_render
+constexpr int kRayWaves = 4;               // rays (waves) per 256-thread block
+constexpr int kScanThreads = 1024;
+constexpr int kScanPerThread = 4;
+constexpr int kScanPart = kScanThreads * kScanPerThread;   // rays per scan partition (4096)
+
+__host__ __device__ inline int64_t mask_words(int64_t n_samples) { return (n_samples + 63) / 64; }
+
+// Workspace: the rays' exclusive kept-sample offsets (int32, padded to 16 B), then their kept masks
+// (mask_words(S) 64-bit words per ray, bit s & 63 of word s >> 6).
+__host__ __device__ inline int64_t offsets_bytes(int64_t n_rays) { return (n_rays * 4 + 15) / 16 * 16; }
+
+inline bool sizes_ok(int64_t n_rays, int64_t n_samples) {
+  return n_rays > 0 && n_samples >= 1 && n_samples <= kMaxSamples && n_rays <= INT_MAX / n_samples;
+}
+
+inline bool grid_ok(int64_t g) { return g >= 32 && g <= 512 && g % 32 == 0; }
+
+// Lanes of this wave below the caller's whose bit is set in m.
+__device__ __forceinline__ int rank_below(unsigned long long m) {
+  return static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(m >> 32),
+                                                    __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(m), 0u)));
+}
+
+// One thread per cell, c = its global index, so a wave's ballot is words c >> 5 and (c >> 5) + 1
+// (G^3 is a multiple of 64: no partial wave).  Occupied: any node of [i - d, i + 1 + d]^3 (clamped
+// to the node grid) above the threshold, or NaN.
+__global__ __launch_bounds__(256) void occupancy_build_kernel(const float* __restrict__ nodes, int g, float threshold,
+                                                              int dilate, unsigned* __restrict__ bits) {
+  const unsigned c = blockIdx.x * 256u + threadIdx.x;
+  const int iz = static_cast<int>(c % g), iy = static_cast<int>((c / g) % g), ix = static_cast<int>(c / (g * g));
+  const int n = g + 1;
+  const int x0 = max(ix - dilate, 0), x1 = min(ix + 1 + dilate, g);
+  const int y0 = max(iy - dilate, 0), y1 = min(iy + 1 + dilate, g);
+  const int z0 = max(iz - dilate, 0), z1 = min(iz + 1 + dilate, g);
+  bool occ = false;
+  for (int x = x0; x <= x1; ++x)
+    for (int y = y0; y <= y1; ++y) {
+      const float* row = nodes + (static_cast<size_t>(x) * n + y) * n;
+      for (int z = z0; z <= z1; ++z) {
+        const float v = row[z];
+        occ = occ || v > threshold || v != v;
+      }
+    }
+  const unsigned long long b = __ballot(occ);
+  const int lane = threadIdx.x & 63;
+  if ((lane & 31) == 0) bits[c >> 5] = static_cast<unsigned>(b >> lane);
+}
+
+// The lookup of include/codenerf.h: u_d = (p_d - lo) inv_cell, each op rounded; inside iff
+// 0 <= u_d < G on every axis (false for NaN), cell floor(u_d).
+__device__ __forceinline__ bool occupied(const unsigned* __restrict__ bits, int g, float lo, float inv_cell,
+                                         float p0, float p1, float p2) {
+  const float u0 = __fmul_rn(__fsub_rn(p0, lo), inv_cell);
+  const float u1 = __fmul_rn(__fsub_rn(p1, lo), inv_cell);
+  const float u2 = __fmul_rn(__fsub_rn(p2, lo), inv_cell);
+  const float gf = static_cast<float>(g);
+  const bool inside = u0 >= 0.0f && u0 < gf && u1 >= 0.0f && u1 < gf && u2 >= 0.0f && u2 < gf;
+  if (!inside) return false;
+  const unsigned i0 = static_cast<unsigned>(static_cast<int>(floorf(u0)));
+  const unsigned i1 = static_cast<unsigned>(static_cast<int>(floorf(u1)));
+  const unsigned i2 = static_cast<unsigned>(static_cast<int>(floorf(u2)));
+  const unsigned c = (i0 * g + i1) * g + i2;      // < G^3 <= 2^27
+  return (bits[c >> 5] >> (c & 31)) & 1u;
+}
+
+// Pass 1, one wave per ray: the kept mask of each 64 samples (a ballot) and the ray's kept count.
+__global__ __launch_bounds__(64 * kRayWaves) void occupancy_mask_kernel(
+    const float* __restrict__ ro, const float* __restrict__ rd, const float* __restrict__ z, int64_t n_rays, int n_samples,
+    const unsigned* __restrict__ bits, int g, float lo, float inv_cell, int* __restrict__ counts,
+    unsigned long long* __restrict__ masks) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = blockIdx.x * static_cast<int64_t>(kRayWaves) + (threadIdx.x >> 6);
+  if (r >= n_rays) return;                 // wave-uniform
+  const float o0 = ro[3 * r], o1 = ro[3 * r + 1], o2 = ro[3 * r + 2];
+  const float d0 = rd[3 * r], d1 = rd[3 * r + 1], d2 = rd[3 * r + 2];
+  const int nw = static_cast<int>(mask_words(n_samples));
+  int total = 0;
+  for (int w = 0; w < nw; ++w) {
+    const int s = 64 * w + lane;
+    bool keep = false;
+    if (s < n_samples) {
+      const float zv = z[r * n_samples + s];
+      keep = occupied(bits, g, lo, inv_cell, cn::mul_add_rn(d0, zv, o0), cn::mul_add_rn(d1, zv, o1),
+                      cn::mul_add_rn(d2, zv, o2));
+    }
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) masks[r * nw + w] = m;
+    total += __popcll(m);
+  }
+  if (lane == 0) counts[r] = total;
+}
+
+// Pass 2, one workgroup: the ray counts -> their exclusive prefix sums, in place, a partition of
+// kScanPart rays per round with the running total carried over; the grand total is M'.
+__global__ __launch_bounds__(kScanThreads) void occupancy_scan_kernel(int* __restrict__ offsets, int64_t n_rays,
+                                                                       int64_t* __restrict__ count) {
+  __shared__ int s_wave[kScanThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int carry = 0;
+  for (int64_t base = 0; base < n_rays; base += kScanPart) {
+    const int64_t i0 = base + static_cast<int64_t>(tid) * kScanPerThread;
+    int v[kScanPerThread];
+    int t = 0;
+#pragma unroll
+    for (int q = 0; q < kScanPerThread; ++q) {
+      v[q] = i0 + q < n_rays ? offsets[i0 + q] : 0;
+      t += v[q];
+    }
+    int incl = t;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int u = __shfl_up(incl, off);
+      if (lane >= off) incl += u;
+    }
+    if (lane == 63) s_wave[wv] = incl;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < kScanThreads / 64; ++k) {
+      const int x = s_wave[k];
+      before += k < wv ? x : 0;
+      all += x;
+    }
+    int run = carry + before + incl - t;
+#pragma unroll
+    for (int q = 0; q < kScanPerThread; ++q) {
+      if (i0 + q < n_rays) offsets[i0 + q] = run;
+      run += v[q];
+    }
+    carry += all;
+    __syncthreads();                       // s_wave is rewritten next round
+  }
+  if (tid == 0) count[0] = carry;
+}
+
+// Pass 3, one wave per ray: kept sample k goes to compact row offset[r] + (kept samples of the ray
+// before it), an mbcnt rank: ascending k.
+__global__ __launch_bounds__(64 * kRayWaves) void occupancy_emit_kernel(
+    const float* __restrict__ ro, const float* __restrict__ rd, const float* __restrict__ z, int64_t n_rays, int n_samples,
+    int64_t chunk_rows, const int64_t* __restrict__ code_index, const int* __restrict__ offsets,
+    const unsigned long long* __restrict__ masks, int* __restrict__ sample_index, float* __restrict__ pts,
+    float* __restrict__ vdir, int64_t* __restrict__ code_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = blockIdx.x * static_cast<int64_t>(kRayWaves) + (threadIdx.x >> 6);
+  if (r >= n_rays) return;                 // wave-uniform
+  const int nw = static_cast<int>(mask_words(n_samples));
+  const float o0 = ro[3 * r], o1 = ro[3 * r + 1], o2 = ro[3 * r + 2];
+  const float d0 = rd[3 * r], d1 = rd[3 * r + 1], d2 = rd[3 * r + 2];
+  // Q1 (decode_sample, mlp_common.h): sample row k of a chunk takes the view direction of ray k mod Rc
+  const int64_t base = (r / chunk_rows) * chunk_rows;
+  const int64_t rcnt = min(chunk_rows, n_rays - base);
+  const int64_t code = code_index ? code_index[r] : r;
+  int64_t j0 = offsets[r];
+  for (int w = 0; w < nw; ++w) {
+    const unsigned long long m = masks[r * nw + w];
+    const int s = 64 * w + lane;
+    if ((m >> lane) & 1ull) {
+      const int64_t j = j0 + rank_below(m);
+      const float zv = z[r * n_samples + s];
+      // (r - base) S + s <= r S + s < n_rays S <= INT_MAX (sizes_ok): a 32-bit remainder
+      const int64_t dray = base + static_cast<unsigned>((r - base) * n_samples + s) % static_cast<unsigned>(rcnt);
+      sample_index[j] = static_cast<int>(r * n_samples + s);
+      pts[3 * j] = cn::mul_add_rn(d0, zv, o0);
+      pts[3 * j + 1] = cn::mul_add_rn(d1, zv, o1);
+      pts[3 * j + 2] = cn::mul_add_rn(d2, zv, o2);
+      vdir[3 * j] = rd[3 * dray];
+      vdir[3 * j + 1] = rd[3 * dray + 1];
+      vdir[3 * j + 2] = rd[3 * dray + 2];
+      if (code_out) code_out[j] = code;
+    }
+    j0 += __popcll(m);
+  }
+}
+
+// The gather back, one wave per ray: a kept sample's compact row, else the empty row; one 16-B
+// store per lane (1 KiB per wave instruction).
+__global__ __launch_bounds__(64 * kRayWaves) void occupancy_expand_kernel(
+    const float4* __restrict__ raw_compact, const int* __restrict__ offsets, const unsigned long long* __restrict__ masks,
+    int64_t n_rays, int n_samples, float4* __restrict__ raw) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = blockIdx.x * static_cast<int64_t>(kRayWaves) + (threadIdx.x >> 6);
+  if (r >= n_rays) return;                 // wave-uniform
+  const int nw = static_cast<int>(mask_words(n_samples));
+  int64_t j0 = offsets[r];
+  for (int w = 0; w < nw; ++w) {
+    const unsigned long long m = masks[r * nw + w];
+    const int s = 64 * w + lane;
+    if (s < n_samples) {
+      float4 v = make_float4(0.0f, 0.0f, 0.0f, CN_EMPTY_SIGMA_RAW);
+      if ((m >> lane) & 1ull) v = raw_compact[j0 + rank_below(m)];
+      raw[r * n_samples + s] = v;
+    }
+    j0 += __popcll(m);
+  }
+}
+
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+}  // namespace
+
+extern "C" int64_t cn_occupancy_cull_workspace_bytes(int64_t n_rays, int64_t n_samples) {
+  if (!sizes_ok(n_rays, n_samples)) return -1;
+  return offsets_bytes(n_rays) + n_rays * mask_words(n_samples) * 8;
+}
+
+extern "C" int cn_occupancy_build(const float* nodes, int64_t g, float threshold, int dilate, uint32_t* bits,
+                                  cn_stream_t stream) {
+  CN_CHECK_ARG(nodes && bits && grid_ok(g) && dilate >= 0 && dilate <= 2);
+  const unsigned blocks = static_cast<unsigned>(g * g * g / 256);      // g % 32 == 0: exact
+  hipLaunchKernelGGL(occupancy_build_kernel, dim3(blocks), dim3(256), 0, cn::as_stream(stream), nodes,
+                     static_cast<int>(g), threshold, dilate, bits);
+  return cn::launch_status();
+}
+
+extern "C" int cn_occupancy_cull(const float* ro, const float* rd, const float* z, int64_t n_rays, int64_t n_samples,
+                                 int64_t chunk_rows, const int64_t* code_index, const uint32_t* bits, int64_t g,
+                                 float lo, float inv_cell, void* workspace, int64_t* count, int32_t* sample_index,
+                                 float* pts, float* vdir, int64_t* code_out, cn_stream_t stream) {
+  CN_CHECK_ARG(ro && rd && z && bits && workspace && count && sample_index && pts && vdir);
+  CN_CHECK_ARG(sizes_ok(n_rays, n_samples) && chunk_rows > 0 && grid_ok(g));
+  CN_CHECK_ARG(aligned8(workspace) && aligned8(count));
+  const int64_t ray_blocks = cn::ceil_div(n_rays, kRayWaves);
+  CN_CHECK_ARG(ray_blocks <= INT_MAX);
+  int* offsets = static_cast<int*>(workspace);
+  unsigned long long* masks =
+      reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + offsets_bytes(n_rays));
+  const int s = static_cast<int>(n_samples);
+  hipStream_t st = cn::as_stream(stream);
+  hipLaunchKernelGGL(occupancy_mask_kernel, dim3(static_cast<unsigned>(ray_blocks)), dim3(64 * kRayWaves), 0, st, ro,
+                     rd, z, n_rays, s, bits, static_cast<int>(g), lo, inv_cell, offsets, masks);
+  hipLaunchKernelGGL(occupancy_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, offsets, n_rays, count);
+  hipLaunchKernelGGL(occupancy_emit_kernel, dim3(static_cast<unsigned>(ray_blocks)), dim3(64 * kRayWaves), 0, st, ro,
+                     rd, z, n_rays, s, chunk_rows, code_index, offsets, masks, sample_index, pts, vdir, code_out);
+  return cn::launch_status();
+}
+
+extern "C" int cn_occupancy_expand(const float* raw_compact, const void* workspace, int64_t n_rays, int64_t n_samples,
+                                   float* raw, cn_stream_t stream) {
+  CN_CHECK_ARG(workspace && raw && sizes_ok(n_rays, n_samples));
+  CN_CHECK_ARG(aligned8(workspace) && cn::aligned16(raw) && cn::aligned16(raw_compact));
+  const int64_t ray_blocks = cn::ceil_div(n_rays, kRayWaves);
+  CN_CHECK_ARG(ray_blocks <= INT_MAX);
+  const int* offsets = static_cast<const int*>(workspace);
+  const unsigned long long* masks =
+      reinterpret_cast<const unsigned long long*>(static_cast<const char*>(workspace) + offsets_bytes(n_rays));
+  hipLaunchKernelGGL(occupancy_expand_kernel, dim3(static_cast<unsigned>(ray_blocks)), dim3(64 * kRayWaves), 0,
+                     cn::as_stream(stream), reinterpret_cast<const float4*>(raw_compact), offsets, masks, n_rays,
+                     static_cast<int>(n_samples), reinterpret_cast<float4*>(raw));
+  return cn::launch_status();
+}

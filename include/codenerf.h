@@ -300,6 +300,68 @@ int cn_density_field(const float* packed, int fmt, const float* code_bias, const
                      const float* x, int64_t x_stride, int64_t n_rays, int64_t n_samples,
                      const float* freqs_xyz, float* sigma, float* raw, cn_stream_t stream);
 
+/* --- Occupancy-grid sample culling (inference) --------------------------
+ * A grid is the cube [-bound, bound]^3 cut into g^3 cells, g a multiple of 32 in [32, 512], one bit
+ * per cell in g^3 / 32 32-bit words of device memory: cell (ix, iy, iz) has linear index
+ * c = (ix g + iy) g + iz and is occupied iff bit c & 31 of word c >> 5 is set.
+ * Point lookup, fp32 with every operation rounded: u_d = (p_d - lo) * inv_cell (the caller passes
+ * lo = -bound and inv_cell = (float)(g / (2 bound))); the point is inside iff 0 <= u_d < g on all
+ * three axes (a NaN coordinate fails), its cell is i_d = (int)floorf(u_d); a point outside the
+ * cube is empty.  A culled sample has exactly zero density -- not the field's softplus tail.
+ * All three entries are stream-ordered, launch on `stream` and never synchronise; argument errors
+ * return CN_EINVAL before any launch. */
+
+/* sigma_raw of a culled slot of cn_occupancy_expand's output: softplus(x - 1) as cn_volume_render
+ * evaluates it is exactly 0 there, so the slot has alpha 0, weight 0 and leaves the transmittance
+ * as it was. */
+#define CN_EMPTY_SIGMA_RAW (-1.0e4f)
+
+/* Grid from node densities: nodes (g+1)^3, axis order [ix, iy, iz], the density at
+ * linspace(-bound, bound, g+1) per axis.  A cell is occupied iff one of the nodes
+ * [i_d - dilate, i_d + 1 + dilate] per axis (clamped to the node grid) is > threshold or NaN:
+ * dilate = 0 tests the cell's 8 corners, dilate 1 or 2 grows that occupancy by as many cells in
+ * Chebyshev distance.  One launch; bits: g^3 / 32 words, all written.
+ * CN_EINVAL: nodes or bits NULL; g not a multiple of 32 in [32, 512]; dilate outside 0..2. */
+int cn_occupancy_build(const float* nodes, int64_t g, float threshold, int dilate, uint32_t* bits,
+                       cn_stream_t stream);
+
+/* Bytes of the state workspace of cn_occupancy_cull / cn_occupancy_expand for (n_rays, n_samples)
+ * (the rays' kept-sample offsets and kept masks), or -1 for sizes those entries refuse. */
+int64_t cn_occupancy_cull_workspace_bytes(int64_t n_rays, int64_t n_samples);
+
+/* Look up every sample k = r n_samples + s at p = ro[r] + rd[r] * z[r][s] (formed as
+ * cn_radiance_field forms it) and compact the occupied ones, in ascending k, into M' rows:
+ *   count[0]        M' (device int64);
+ *   sample_index[j] k (int32);
+ *   pts[j]          p (3 floats);
+ *   vdir[j]         the UNNORMALISED rd row of the sample's Q1 view-direction ray (chunk_rows as in
+ *                   cn_radiance_field: base = (r / chunk_rows) chunk_rows, rcnt = min(chunk_rows,
+ *                   n_rays - base), ray base + ((r - base) n_samples + s) % rcnt);
+ *   code_out[j]     (int64, optional) code_index ? code_index[r] : r.
+ * Every output holds n_rays * n_samples rows, of which the first M' are written.  The rows are a
+ * points-mode input of cn_radiance_field, cn_radiance_field_fold and cn_density_field -- pts, rd =
+ * vdir, n_rays = chunk_rows = M', n_samples = 1, code_index = code_out (or none with one code
+ * row) -- which computes for each the bits the unculled field computes for sample k.
+ * workspace: cn_occupancy_cull_workspace_bytes(n_rays, n_samples) bytes, 8-byte aligned, written
+ * here and read by cn_occupancy_expand.  Three launches (masks, a scan of the rays' counts, emit):
+ * no atomics, the result is deterministic.
+ * CN_EINVAL: a required pointer NULL (code_index and code_out are optional); n_rays <= 0;
+ * n_samples outside 1..512; n_rays * n_samples > INT32_MAX; chunk_rows <= 0; g as above; workspace
+ * or count not 8-byte aligned. */
+int cn_occupancy_cull(const float* ro, const float* rd, const float* z, int64_t n_rays, int64_t n_samples,
+                      int64_t chunk_rows, const int64_t* code_index, const uint32_t* bits, int64_t g,
+                      float lo, float inv_cell, void* workspace, int64_t* count, int32_t* sample_index,
+                      float* pts, float* vdir, int64_t* code_out, cn_stream_t stream);
+
+/* The gather back: raw (n_rays, n_samples, 4) row k = raw_compact (M', 4) row j where
+ * sample_index[j] = k, and [0, 0, 0, CN_EMPTY_SIGMA_RAW] for a culled k.  workspace: as
+ * cn_occupancy_cull of the same sizes left it.  raw and raw_compact 16-byte aligned; raw_compact
+ * may be NULL only when the caller knows M' = 0.
+ * CN_EINVAL: workspace or raw NULL; a size cn_occupancy_cull refuses; raw or raw_compact
+ * misaligned; workspace not 8-byte aligned. */
+int cn_occupancy_expand(const float* raw_compact, const void* workspace, int64_t n_rays, int64_t n_samples,
+                        float* raw, cn_stream_t stream);
+
 /* --- Backward (autograd through the eval / train step) ------------------
  * The gradients loss.backward() takes through the path in the reference's
  * test-time optimisation (view_synthesis/eval.py) and training step:
