@@ -235,6 +235,34 @@ def _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy: 
         return ops.occupancy_expand(raw, state)
 
 
+def _weight_culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, tolerance: float,
+                         occupancy: Optional[OccupancyGrid]):
+    """The fine field call under ``rgb_tolerance``: densities of every sample (the density kernel, under
+    the grid when there is one) -> the render's own weights -> cull by weight -> ``model``'s inference
+    field in points mode over the kept samples, its colours scattered into the density rows -> raw
+    (R, S, 4).  Every row keeps its sigma_raw; a culled one has raw colours [0, 0, 0]."""
+    from ..models.model import _field_op
+    fx, fd = _check_embedders(embedders)
+    cs, ct, code_index = _codes(z_s, z_t)
+    m = _unwrap(model)
+    with torch.no_grad():
+        ro, rd = ro.detach(), rd.detach()
+        if occupancy is None:
+            raw = _density_field_raw(model, embedders, rd, z_s, z_t, chunk_rows, ro=ro, z=z)
+        else:       # the grid's empty rows have weight exactly 0: they fall out by w > 0
+            raw = _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy, density_only=True)
+        weights = ops.volume_render(raw, z, rd)[3]
+        eps_weight, eps_tail = ops.weight_cull_thresholds(tolerance, z.shape[1])
+        many = cs.shape[0] > 1
+        count, sample_index, pts, vdir, code_out, _ = ops.weight_cull(
+            weights, ro, rd, z, chunk_rows, eps_weight, eps_tail, code_index=code_index, want_code=many)
+        if count:
+            kept = _field_op(m, cs.detach(), ct.detach(), vdir, count, fx, fd, pts=pts.view(count, 1, 3),
+                             code_index=code_out if many else None)
+            ops.scatter_rgb(kept, sample_index, raw)
+        return raw
+
+
 def forward_pass(model, embedders, rd: torch.Tensor, pts: torch.Tensor,
                  object_embedding: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
     """nerf/__init__.py:94-134: embed + MLP for one chunk -> (R, S, 4).
@@ -251,7 +279,8 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
                 point_sampler: PointSampler, embedders, coarse_model, fine_model=None, chunk_rows: Optional[int] = None,
                 t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
                 coarse_only: bool = False, events: Optional[dict] = None,
-                coarse_rgb: bool = True, occupancy: Optional[OccupancyGrid] = None) -> Dict[str, torch.Tensor]:
+                coarse_rgb: bool = True, occupancy: Optional[OccupancyGrid] = None,
+                rgb_tolerance: Optional[float] = None) -> Dict[str, torch.Tensor]:
     """predict_radiance_and_render over a whole ray list, chunk semantics kept via ``chunk_rows``.
 
     Returns rgb/depth/acc for the coarse pass (+ weights) and, unless
@@ -268,12 +297,31 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     a culled sample has exactly zero density (not the reference's softplus tail), a kept one the
     unculled call's bits.  The kept count is read back on the host once per field call, so this
     render is not graph-capturable.
+    ``rgb_tolerance`` (inference only; needs a fine pass): a bound on the weight the fine pass may leave
+    uncoloured per ray.  The fine pass then runs the density kernel over every fine sample, forms the
+    render's weights from those densities, and runs the colour layers only for the samples kept by
+    include/codenerf.h's rule with eps_tail = tol / 2 and eps_weight = the largest float32 <=
+    tol / (2 S); a culled sample keeps its density and composites the colour 0.5.  "depth_fine",
+    "acc_fine", "disp_fine" and the coarse entries are bitwise the plain call's; each channel of
+    "rgb_fine" is within 0.501 x (the ray's culled weight, <= tol) of it, plus fp32 summation rounding.
+    0.0 culls only samples of weight 0 or NaN.  Composes with ``occupancy``.  The kept count is read
+    back on the host once (ops.weight_cull), so this render is not graph-capturable either.
     """
-    if not coarse_rgb or occupancy is not None:
+    if rgb_tolerance is not None:
+        rgb_tolerance = float(rgb_tolerance)
+        if not rgb_tolerance >= 0.0:
+            raise ValueError(f"rgb_tolerance must be >= 0 and not NaN, got {rgb_tolerance}")
+        if coarse_only or fine_model is None:
+            raise ValueError("rgb_tolerance bounds the fine pass's colours: there is none to apply it to with "
+                             "coarse_only=True (or without a fine model)")
+    if not coarse_rgb or occupancy is not None or rgb_tolerance is not None:
         if torch.is_grad_enabled() and (
                 any(t is not None and t.requires_grad for t in (ro, rd, z_s, z_t)) or
                 any(p.requires_grad for m in (coarse_model, fine_model) if m is not None
                     for p in _unwrap(m).param_list())):
+            if rgb_tolerance is not None:
+                raise ValueError("rgb_tolerance is an inference render: the two-phase fine pass has no backward "
+                                 "(render under torch.no_grad(), or pass rgb_tolerance=None)")
             if coarse_rgb:
                 raise ValueError("occupancy culling is an inference render: the compacted field has no backward "
                                  "(render under torch.no_grad(), or pass occupancy=None)")
@@ -306,7 +354,10 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
         coarse_field, fine_field = culled(not coarse_rgb), culled(False)
     else:
         coarse_field, fine_field = (_field if coarse_rgb else _density_field_raw), _field
-    if fine_model is not None and not coarse_only and coarse_rgb and occupancy is None:
+    if rgb_tolerance is not None:
+        def fine_field(model, embedders, rd, z_s, z_t, chunk_rows, ro=None, z=None, pair=None):
+            return _weight_culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, rgb_tolerance, occupancy)
+    if fine_model is not None and not coarse_only and coarse_rgb and occupancy is None and rgb_tolerance is None:
         # the two differentiable fields' pre-field launches (code terms, packs, zeroed accumulators) as
         # one launch; each field takes its part (no launch when either runs without gradients)
         from ..autograd import new_field_pair, prefetch_render_prepares
@@ -349,7 +400,8 @@ def predict_radiance_and_render(rays: Tuple[torch.Tensor, torch.Tensor], point_s
 
 def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, samplers, embedders, device,
                           key: str = "rgb_fine", coarse_only: bool = False,
-                          coarse_rgb: bool = True, occupancy: Optional[OccupancyGrid] = None) -> Optional[torch.Tensor]:
+                          coarse_rgb: bool = True, occupancy: Optional[OccupancyGrid] = None,
+                          rgb_tolerance: Optional[float] = None) -> Optional[torch.Tensor]:
     """nerf/__init__.py:137-226: shard the image's rays over ranks, render, gather on rank 0.
 
     The split is the reference's (Q5: truncating, the last rank takes the
@@ -359,6 +411,7 @@ def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, sam
     per-rank rows.  Rank 0 returns (H*W, 3); the others return None.
     ``coarse_rgb=False``: the coarse pass computes densities only (render_rays); ``key`` cannot then
     be "rgb_coarse".  ``occupancy``: an OccupancyGrid of the object, for render_rays' sample culling.
+    ``rgb_tolerance``: render_rays' bound for the fine pass's weight-based colour culling.
     """
     if not coarse_rgb and key == "rgb_coarse":
         raise ValueError('coarse_rgb=False renders no coarse colours: key="rgb_coarse" needs coarse_rgb=True')
@@ -382,7 +435,8 @@ def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, sam
         z_t = z_t.to(device).expand(num_rays, -1)[sl]
         out = render_rays(ro[sl].to(device), rd[sl].to(device), z_s, z_t, point_sampler, embedders,
                           models["nerf_coarse"], models.get("nerf_fine"), cfg.nerf.validation.chunksize,
-                          coarse_only=coarse_only, coarse_rgb=coarse_rgb, occupancy=occupancy)
+                          coarse_only=coarse_only, coarse_rgb=coarse_rgb, occupancy=occupancy,
+                          rgb_tolerance=rgb_tolerance)
         rgb = out[key]
         if not is_distributed:
             return rgb

@@ -9,6 +9,7 @@ PyTorch compute.
 from __future__ import annotations
 
 import ctypes
+import struct
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -605,6 +606,87 @@ def occupancy_expand(raw_compact: Optional[Tensor], state) -> Tensor:
     if n * s:
         check(lib.cn_occupancy_expand(ptr(raw_compact), ptr(workspace), n, s, ptr(raw), stream_of(raw)),
               "cn_occupancy_expand")
+    return raw
+
+
+# ------------------------------------------------------------------ weight-bounded colour culling
+
+
+def float32_floor(x: float) -> float:
+    """The largest float32 <= ``x`` (x finite, >= 0), as a Python float."""
+    f = struct.unpack("<f", struct.pack("<f", x))[0]          # round to nearest
+    if f > x:
+        f = struct.unpack("<f", struct.pack("<I", struct.unpack("<I", struct.pack("<f", f))[0] - 1))[0]
+    return f
+
+
+def weight_cull_thresholds(tolerance: float, n_samples: int) -> Tuple[float, float]:
+    """(eps_weight, eps_tail) of a colour tolerance on a ray of ``n_samples`` samples (include/codenerf.h):
+    the largest float32 <= tol / (2 S), and tol / 2; the culled weights of a ray then sum to <= tol."""
+    return float32_floor(tolerance / (2.0 * n_samples)), tolerance / 2.0
+
+
+def weight_cull(weights: Tensor, ro: Tensor, rd: Tensor, z: Tensor, chunk_rows: int, eps_weight: float,
+                eps_tail: float, code_index: Optional[Tensor] = None, want_code: bool = True):
+    """Compact the samples whose volume-render weight can matter (cn_weight_cull): sample i of a ray is
+    kept iff w_i > 0, w_i >= eps_weight (fp32) and the double sum of w_i.. >= eps_tail; NaN fails.
+    ``weights`` (R, S) as volume_render returns them -> occupancy_cull's tuple (count, sample_index,
+    pts, vdir, code_out or None, state), the kept samples in ascending order; ``state`` is valid for
+    occupancy_expand.
+
+    Like occupancy_cull, this reads ``count`` back once (``.item()``): a HOST SYNCHRONISATION, since
+    the field launch over the kept rows is sized by it."""
+    lib = _lib_ready()
+    weights = _cuda(weights, "weights")
+    ro, rd, z = _cuda(ro, "ro"), _cuda(rd, "rd"), _cuda(z, "z_vals")
+    assert z.dim() == 2, "z must be (num_rays, num_samples)"
+    n, s = z.shape
+    assert weights.shape == (n, s), "weights must be (num_rays, num_samples)"
+    assert ro.shape == (n, 3) and rd.shape == (n, 3), "ro / rd must be (num_rays, 3)"
+    eps_weight, eps_tail = float(eps_weight), float(eps_tail)
+    if not (eps_weight >= 0.0 and eps_tail >= 0.0):
+        raise ValueError(f"weight_cull: thresholds must be >= 0 and not NaN (got {eps_weight}, {eps_tail})")
+    if code_index is not None:
+        code_index = _cuda(code_index, "code_index", torch.int64)
+        assert code_index.shape == (n,), "code_index must be (num_rays,)"
+    dev = z.device
+    m = n * s
+    sample_index = torch.empty(m, device=dev, dtype=torch.int32)
+    pts = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    vdir = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    code_out = torch.empty(m, device=dev, dtype=torch.int64) if want_code else None
+    if m == 0:
+        return 0, sample_index, pts, vdir, code_out, (None, n, s, 0)
+    ws_bytes = lib.cn_occupancy_cull_workspace_bytes(n, s)
+    if ws_bytes < 0:
+        raise ValueError(f"weight_cull: {n} rays x {s} samples is outside 1..512 samples / 2^31 - 1 rows")
+    workspace = torch.empty((ws_bytes + 7) // 8, device=dev, dtype=torch.int64)
+    count = torch.empty(1, device=dev, dtype=torch.int64)
+    check(lib.cn_weight_cull(ptr(weights), ptr(ro), ptr(rd), ptr(z), n, s, int(chunk_rows), ptr(code_index),
+                             eps_weight, eps_tail, ptr(workspace), ptr(count), ptr(sample_index), ptr(pts), ptr(vdir),
+                             ptr(code_out), stream_of(z)), "cn_weight_cull")
+    k = int(count.item())       # host synchronisation (see the docstring)
+    return (k, sample_index[:k], pts[:k], vdir[:k], None if code_out is None else code_out[:k],
+            (workspace, n, s, k))
+
+
+def scatter_rgb(raw_compact: Tensor, sample_index: Tensor, raw: Tensor) -> Tensor:
+    """The colours of the compact field rows (M', 4) into ``raw`` (.., 4) IN PLACE (cn_scatter_rgb):
+    components 0..2 of row ``sample_index[j]`` from compact row j; component 3 (sigma_raw) and every
+    other row stay as they are -> ``raw``.  Nothing is launched when no row was kept."""
+    lib = _lib_ready()
+    sample_index = _cuda(sample_index, "sample_index", torch.int32)
+    k = sample_index.shape[0]
+    assert raw.is_cuda and raw.dtype == torch.float32 and raw.is_contiguous() and raw.shape[-1] == 4 and \
+        raw.data_ptr() % 16 == 0, "raw must be a contiguous, 16-B aligned (.., 4) float32 device tensor"
+    n_slots = raw.numel() // 4
+    assert sample_index.dim() == 1 and k <= n_slots, "sample_index must be (M',) with M' <= raw's rows"
+    if k == 0:
+        return raw
+    raw_compact = _aligned16(_cuda(raw_compact, "raw_compact").reshape(-1, 4))
+    assert raw_compact.shape[0] == k, f"raw_compact must hold the {k} kept rows"
+    check(lib.cn_scatter_rgb(ptr(raw_compact), ptr(sample_index), k, ptr(raw), n_slots, stream_of(raw)),
+          "cn_scatter_rgb")
     return raw
 
 

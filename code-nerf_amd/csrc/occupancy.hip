@@ -10,6 +10,10 @@
 //   expand  the compact (M', 4) result gathered back to (R, S, 4), culled slots the empty row.
 // All three are bandwidth / latency bound: one wave per ray, ballots and mbcnt ranks, no atomics, so
 // the compact order (and with it every output) is deterministic.
+//
+// Weight-bounded colour culling (cn_weight_cull, cn_scatter_rgb) reuses passes 2 and 3 and the
+// workspace: its pass 1 decides from a ray's volume-render weights instead of a grid, and the
+// compact field result goes back through a colours-only scatter instead of the expand.
 #include <limits.h>
 
 #include "cn_common.h"
@@ -213,7 +217,80 @@ __global__ __launch_bounds__(64 * kRayWaves) void occupancy_expand_kernel(
   }
 }
 
+// Weight culling, pass 1, one wave per ray: sample i is kept iff w_i > 0, w_i >= eps_weight and
+// tail_i = sum_{k >= i} (double)w_k >= eps_tail (NaN fails each).  The 64-sample words are taken from
+// the last to the first; in a word the doubles go through an inclusive suffix scan across the lanes
+// (log-step shuffles: lane l adds lanes l + 1, l + 2, l + 4, ...), then the sum of the later words
+// (the previous word's lane-0 tail) is added.  Masks and counts as occupancy_mask_kernel leaves them.
+__global__ __launch_bounds__(64 * kRayWaves) void weight_mask_kernel(
+    const float* __restrict__ weights, int64_t n_rays, int n_samples, float eps_weight, double eps_tail,
+    int* __restrict__ counts, unsigned long long* __restrict__ masks) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = blockIdx.x * static_cast<int64_t>(kRayWaves) + (threadIdx.x >> 6);
+  if (r >= n_rays) return;                 // wave-uniform
+  const int nw = static_cast<int>(mask_words(n_samples));
+  double carry = 0.0;
+  int total = 0;
+  for (int w = nw - 1; w >= 0; --w) {
+    const int s = 64 * w + lane;
+    const float wv = s < n_samples ? weights[r * n_samples + s] : 0.0f;
+    double tail = static_cast<double>(wv);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const double u = __shfl_down(tail, off);
+      if (lane + off < 64) tail += u;
+    }
+    tail += carry;
+    carry = __shfl(tail, 0);
+    const bool keep = wv > 0.0f && wv >= eps_weight && tail >= eps_tail;
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) masks[r * nw + w] = m;
+    total += __popcll(m);
+  }
+  if (lane == 0) counts[r] = total;
+}
+
+// The colours of the kept rows back into raw (n_slots, 4): one thread per compact row, a 16-B load
+// and a 12-B store; component 3 (sigma_raw) and every other row are not written.
+__global__ __launch_bounds__(256) void scatter_rgb_kernel(const float4* __restrict__ raw_compact,
+                                                          const int* __restrict__ sample_index, int n_rows,
+                                                          float* __restrict__ raw, int n_slots) {
+  const int j = static_cast<int>(blockIdx.x * 256u + threadIdx.x);
+  if (j >= n_rows) return;
+  const int k = sample_index[j];
+  if (static_cast<unsigned>(k) >= static_cast<unsigned>(n_slots)) return;   // never a store outside raw
+  const float4 v = raw_compact[j];
+  *reinterpret_cast<float3*>(raw + 4 * static_cast<size_t>(k)) = make_float3(v.x, v.y, v.z);
+}
+
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// What the two cull entries share: their common argument rules ...
+inline bool cull_args_ok(const float* ro, const float* rd, const float* z, int64_t n_rays, int64_t n_samples,
+                         int64_t chunk_rows, const void* workspace, const int64_t* count,
+                         const int32_t* sample_index, const float* pts, const float* vdir) {
+  return ro && rd && z && workspace && count && sample_index && pts && vdir && sizes_ok(n_rays, n_samples) &&
+         chunk_rows > 0 && aligned8(workspace) && aligned8(count) && cn::ceil_div(n_rays, kRayWaves) <= INT_MAX;
+}
+
+inline int* ws_offsets(void* workspace) { return static_cast<int*>(workspace); }
+
+inline unsigned long long* ws_masks(void* workspace, int64_t n_rays) {
+  return reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + offsets_bytes(n_rays));
+}
+
+// ... and passes 2 and 3 over the masks and counts their pass 1 left in the workspace.
+inline int launch_scan_emit(const float* ro, const float* rd, const float* z, int64_t n_rays, int64_t n_samples,
+                            int64_t chunk_rows, const int64_t* code_index, void* workspace, int64_t* count,
+                            int32_t* sample_index, float* pts, float* vdir, int64_t* code_out, hipStream_t st) {
+  const unsigned ray_blocks = static_cast<unsigned>(cn::ceil_div(n_rays, kRayWaves));
+  int* offsets = ws_offsets(workspace);
+  hipLaunchKernelGGL(occupancy_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, offsets, n_rays, count);
+  hipLaunchKernelGGL(occupancy_emit_kernel, dim3(ray_blocks), dim3(64 * kRayWaves), 0, st, ro, rd, z, n_rays,
+                     static_cast<int>(n_samples), chunk_rows, code_index, offsets, ws_masks(workspace, n_rays),
+                     sample_index, pts, vdir, code_out);
+  return cn::launch_status();
+}
 
 }  // namespace
 
@@ -235,21 +312,37 @@ extern "C" int cn_occupancy_cull(const float* ro, const float* rd, const float* 
                                  int64_t chunk_rows, const int64_t* code_index, const uint32_t* bits, int64_t g,
                                  float lo, float inv_cell, void* workspace, int64_t* count, int32_t* sample_index,
                                  float* pts, float* vdir, int64_t* code_out, cn_stream_t stream) {
-  CN_CHECK_ARG(ro && rd && z && bits && workspace && count && sample_index && pts && vdir);
-  CN_CHECK_ARG(sizes_ok(n_rays, n_samples) && chunk_rows > 0 && grid_ok(g));
-  CN_CHECK_ARG(aligned8(workspace) && aligned8(count));
-  const int64_t ray_blocks = cn::ceil_div(n_rays, kRayWaves);
-  CN_CHECK_ARG(ray_blocks <= INT_MAX);
-  int* offsets = static_cast<int*>(workspace);
-  unsigned long long* masks =
-      reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + offsets_bytes(n_rays));
-  const int s = static_cast<int>(n_samples);
+  CN_CHECK_ARG(bits && grid_ok(g));
+  CN_CHECK_ARG(cull_args_ok(ro, rd, z, n_rays, n_samples, chunk_rows, workspace, count, sample_index, pts, vdir));
   hipStream_t st = cn::as_stream(stream);
-  hipLaunchKernelGGL(occupancy_mask_kernel, dim3(static_cast<unsigned>(ray_blocks)), dim3(64 * kRayWaves), 0, st, ro,
-                     rd, z, n_rays, s, bits, static_cast<int>(g), lo, inv_cell, offsets, masks);
-  hipLaunchKernelGGL(occupancy_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, offsets, n_rays, count);
-  hipLaunchKernelGGL(occupancy_emit_kernel, dim3(static_cast<unsigned>(ray_blocks)), dim3(64 * kRayWaves), 0, st, ro,
-                     rd, z, n_rays, s, chunk_rows, code_index, offsets, masks, sample_index, pts, vdir, code_out);
+  hipLaunchKernelGGL(occupancy_mask_kernel, dim3(static_cast<unsigned>(cn::ceil_div(n_rays, kRayWaves))),
+                     dim3(64 * kRayWaves), 0, st, ro, rd, z, n_rays, static_cast<int>(n_samples), bits,
+                     static_cast<int>(g), lo, inv_cell, ws_offsets(workspace), ws_masks(workspace, n_rays));
+  return launch_scan_emit(ro, rd, z, n_rays, n_samples, chunk_rows, code_index, workspace, count, sample_index, pts,
+                          vdir, code_out, st);
+}
+
+extern "C" int cn_weight_cull(const float* weights, const float* ro, const float* rd, const float* z, int64_t n_rays,
+                              int64_t n_samples, int64_t chunk_rows, const int64_t* code_index, float eps_weight,
+                              double eps_tail, void* workspace, int64_t* count, int32_t* sample_index, float* pts,
+                              float* vdir, int64_t* code_out, cn_stream_t stream) {
+  CN_CHECK_ARG(weights && eps_weight >= 0.0f && eps_tail >= 0.0);          // a NaN threshold fails
+  CN_CHECK_ARG(cull_args_ok(ro, rd, z, n_rays, n_samples, chunk_rows, workspace, count, sample_index, pts, vdir));
+  hipStream_t st = cn::as_stream(stream);
+  hipLaunchKernelGGL(weight_mask_kernel, dim3(static_cast<unsigned>(cn::ceil_div(n_rays, kRayWaves))),
+                     dim3(64 * kRayWaves), 0, st, weights, n_rays, static_cast<int>(n_samples), eps_weight, eps_tail,
+                     ws_offsets(workspace), ws_masks(workspace, n_rays));
+  return launch_scan_emit(ro, rd, z, n_rays, n_samples, chunk_rows, code_index, workspace, count, sample_index, pts,
+                          vdir, code_out, st);
+}
+
+extern "C" int cn_scatter_rgb(const float* raw_compact, const int32_t* sample_index, int64_t n_rows, float* raw,
+                              int64_t n_slots, cn_stream_t stream) {
+  CN_CHECK_ARG(raw_compact && sample_index && raw && n_slots <= INT_MAX && n_rows >= 1 && n_rows <= n_slots);
+  CN_CHECK_ARG(cn::aligned16(raw_compact) && cn::aligned16(raw));
+  hipLaunchKernelGGL(scatter_rgb_kernel, dim3(static_cast<unsigned>(cn::ceil_div(n_rows, 256))), dim3(256), 0,
+                     cn::as_stream(stream), reinterpret_cast<const float4*>(raw_compact), sample_index,
+                     static_cast<int>(n_rows), raw, static_cast<int>(n_slots));
   return cn::launch_status();
 }
 

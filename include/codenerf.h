@@ -362,6 +362,47 @@ int cn_occupancy_cull(const float* ro, const float* rd, const float* z, int64_t 
 int cn_occupancy_expand(const float* raw_compact, const void* workspace, int64_t n_rays, int64_t n_samples,
                         float* raw, cn_stream_t stream);
 
+/* --- Weight-bounded colour culling (inference) --------------------------
+ * A ray's volume-render weights depend on its densities alone, so a pass that has the densities of
+ * every sample (cn_density_field) and their weights (cn_volume_render) can leave out the colour
+ * layers of the samples whose weight cannot matter.  For one ray with fp32 weights w[0..S-1]:
+ *   tail_i = sum_{k >= i} (double)w_k, accumulated in double;
+ *   sample i is KEPT iff w_i > 0, w_i >= eps_weight (an fp32 comparison) and tail_i >= (double)eps_tail.
+ * A NaN fails every test: a NaN sample, and every sample before it (their tails are NaN), is culled.
+ * Order of the double additions: the samples in words of 64 (word v = samples 64 v .. 64 v + 63,
+ * missing ones 0), the last word first; in a word, lane l's sum is built in log steps (+ lane l + 1,
+ * + the pair at l + 2, + the four at l + 4, ...), then the total of the later words is added.  For
+ * weights that are multiples of 2^-30 (any sum of <= 512 of them below 2^23 is exact) every order
+ * gives the same tails.
+ * A caller with a tolerance tol on the composited colour passes eps_tail = tol / 2 and eps_weight =
+ * the largest float <= tol / (2 S): the culled tail of a ray then sums to < tol / 2 and each of the
+ * at most S other culled samples is < tol / (2 S), so the culled weights of a ray sum to <= tol.
+ * A culled sample keeps its sigma_raw and takes raw colours [0, 0, 0], which composite as 0.5, while
+ * a true colour lies in [-0.001, 1.001]: weights, depth, acc and disp keep the plain render's bits
+ * and each colour channel moves by <= 0.501 * (the ray's culled weight) <= 0.501 tol, plus the fp32
+ * rounding of the two S-term sums compared. */
+
+/* cn_occupancy_cull with the kept test above in place of the grid lookup: weights (n_rays,
+ * n_samples) as cn_volume_render wrote them.  Every output, the workspace
+ * (cn_occupancy_cull_workspace_bytes) and its layout are cn_occupancy_cull's -- the same scan and
+ * emit launches follow the mask launch -- so cn_occupancy_expand reads the state it leaves.
+ * Stream-ordered, no atomics, compact rows in ascending k.
+ * CN_EINVAL before any launch: weights NULL; eps_weight or eps_tail negative or NaN; and every
+ * size, pointer and alignment rule of cn_occupancy_cull. */
+int cn_weight_cull(const float* weights, const float* ro, const float* rd, const float* z, int64_t n_rays,
+                   int64_t n_samples, int64_t chunk_rows, const int64_t* code_index, float eps_weight,
+                   double eps_tail, void* workspace, int64_t* count, int32_t* sample_index, float* pts,
+                   float* vdir, int64_t* code_out, cn_stream_t stream);
+
+/* Components 0..2 of raw (n_slots, 4) row sample_index[j] = those of raw_compact (n_rows, 4) row j,
+ * for j < n_rows; component 3 (sigma_raw) and every row not indexed are left as they are, so what
+ * cn_volume_render derives from the densities cannot change.  An index outside 0..n_slots - 1
+ * writes nothing.  Rows must be indexed at most once (cn_weight_cull's are).  One launch.
+ * CN_EINVAL: a pointer NULL; n_rows outside 1..n_slots; n_slots > INT32_MAX; raw_compact or raw not
+ * 16-byte aligned. */
+int cn_scatter_rgb(const float* raw_compact, const int32_t* sample_index, int64_t n_rows, float* raw,
+                   int64_t n_slots, cn_stream_t stream);
+
 /* --- Backward (autograd through the eval / train step) ------------------
  * The gradients loss.backward() takes through the path in the reference's
  * test-time optimisation (view_synthesis/eval.py) and training step:
