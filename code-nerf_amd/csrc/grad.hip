@@ -435,7 +435,7 @@ __device__ __forceinline__ void x3_stage(const float* slot, int i, int h, int n0
 // A stage ("unit") is such a row block, units are ordered (direction group g of 16, j) and each
 // workgroup streams a contiguous run of units; it sums its dPre rows per direction (column sums per
 // stage row) and stores them per (workgroup, group) run into gsum slot (workgroup + g), 16 x 256
-// floats.  dir_enc_dw_kernel then forms dW[:, 256:283] = sum_d dsum[d]^T enc(d) and the bias from
+// floats.  dir_enc_dw_block then forms dW[:, 256:283] = sum_d dsum[d]^T enc(d) and the bias from
 // them -- the encodings are evaluated once per direction instead of once per sample, and the
 // (M, 256) dPre plane is streamed once instead of twice (by gemm_tn_enc_kernel as well).
 struct DirFold {
@@ -645,16 +645,17 @@ __device__ __forceinline__ void tn256_body(float* ring, const float* __restrict_
     }
   }
 }
-// One dW GEMM per launch (gemm_tn's whole-tile plan).
-template <bool X3, bool SIG, bool DIRS = false>
+// One dW GEMM per launch (gemm_tn's whole-tile plan; the DIRS fold runs only as a job of the batched
+// launch below).
+template <bool X3, bool SIG>
 __global__ __launch_bounds__(512, 2) void gemm_tn256_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                             float* __restrict__ C, int64_t ldc, float* __restrict__ part,
                                                             float* __restrict__ bias_part, const float* __restrict__ draw,
                                                             float* __restrict__ sig_part, int64_t M,
-                                                            int64_t rows_per_block, DirFold dir = {}) {
+                                                            int64_t rows_per_block) {
   __shared__ __attribute__((aligned(16))) float ring[kTwRing * kTwStage];
-  tn256_body<X3, SIG, DIRS>(ring, A, B, C, ldc, part, bias_part, draw, sig_part, M, rows_per_block, dir, blockIdx.x,
-                            gridDim.x);
+  tn256_body<X3, SIG, false>(ring, A, B, C, ldc, part, bias_part, draw, sig_part, M, rows_per_block, DirFold{},
+                             blockIdx.x, gridDim.x);
 }
 
 // Several whole-tile dW GEMMs in ONE launch (a training backward's four 256 x 256 layers): job k
@@ -1082,15 +1083,15 @@ __device__ __forceinline__ void ring_read8(const float* p, float* v) {
       : "memory");
 }
 
-// The second half of the DIRS fold (gemm_tn256_kernel): workgroup w of this kernel takes direction
-// groups kDirGroups w .. + kDirGroups - 1; per group it adds the gsum slots of the tn256 workgroups
+// The second half of the DIRS fold (the batched launch's kind-2 job): workgroup w of this role takes
+// direction groups kDirGroups w .. + kDirGroups - 1; per group it adds the gsum slots of the tn256 workgroups
 // whose unit runs cover it (in workgroup order), evaluates the 16 directions' encodings with
 // gemm_tn_enc_kernel's arithmetic (PositionalEmbedder order: raw 0..2, then per frequency sin 3,
 // cos 3) and accumulates thread n's row of dW: part[w][n][k] = sum_d dsum[d][n] enc(d)[k], k < 27;
 // the bias (enc 1) into bias_part[w][n].  Fixed order throughout: deterministic.
 constexpr int kDirGroups = 1;
-// Workgroup blk of that launch; threads 0..255 work (a 512-thread caller's upper half only takes
-// part in the barriers: the role rides in gemm_tn_enc_kernel's launch).
+// Workgroup blk of that role; threads 0..255 work (a 512-thread caller's upper half only takes
+// part in the barriers: the role rides in gemm_tn_xenc_kernel's launch).
 __device__ __forceinline__ void dir_enc_dw_block(const mlp::FieldArgs& a, const DirFold& dir, float* __restrict__ part,
                                                  float* __restrict__ bias_part, unsigned blk) {
   __shared__ float encl[16][28];
@@ -1145,9 +1146,11 @@ __device__ __forceinline__ void dir_enc_dw_block(const mlp::FieldArgs& a, const 
   bias_part[(int64_t)blk * 256 + n] = acc[27];
 }
 
-// The DIRS fold's second half as a role of this launch (gemm_tn_enc_kernel's first n workgroups run
-// dir_enc_dw_block instead of a separate 256-workgroup launch): both only need the batched dW launch's
-// outputs (gsum / dPre planes), and their partials go to the same deferred reduction.
+// The DIRS fold's second half as a role of layer_xyz1's launch (gemm_tn_xenc_kernel's first n workgroups
+// run dir_enc_dw_block instead of a separate 256-workgroup launch): both only need the batched dW launch's
+// outputs (gsum / dPre planes), and their partials go to the same deferred reduction.  gemm_tn_enc_kernel
+// takes the same argument, but the host always gives it an empty role: without the block-role test the
+// compiler allocates the kernel's registers and LDS differently, so its source stays as it was measured.
 struct DirRole {
   DirFold dir;
   float* part;
@@ -1502,7 +1505,9 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_xenc_kernel(const float* __res
   xenc_body(A, X, M, part, bias_part, rows_per_block, a, dr, blockIdx.x);
 }
 
-// One field's layer_xyz1 dW pass (gemm_tn_xenc_kernel's arguments).
+// One field's share of a gemm_tn_xenc2_kernel launch (gemm_tn_xenc_kernel's arguments).  The host fills
+// only a and dr: a paired field's row pass runs as the XENC job of the batched launch, so its row
+// arguments stay null / 0 and the field has no row blocks here.
 struct XencJob {
   const float* A;
   const float* X;
@@ -1514,10 +1519,11 @@ struct XencJob {
   DirRole dr;
 };
 
-// A render's two fields' layer_xyz1 dW passes in one launch: workgroups 0 .. first1 - 1 are field j0's
+// A render's two fields' gemm_tn_xenc_kernel launches in one: workgroups 0 .. first1 - 1 are field j0's
 // launch (its DIRS role blocks, then its row blocks), the rest field j1's -- each the same blocks with the
-// same rows as its own launch (bitwise the same partials).  Two instances of the body, each reading its
-// own kernel argument (no runtime select between the structs).
+// same rows as its own launch (bitwise the same partials).  The host launches it with the DIRS role blocks
+// alone (the paired fields' row passes are XENC jobs of the batched launch).  Two instances of the body,
+// each reading its own kernel argument (no runtime select between the structs).
 __global__ __launch_bounds__(512, 1) void gemm_tn_xenc2_kernel(XencJob j0, XencJob j1, unsigned first1) {
   if (blockIdx.x >= first1)
     xenc_body(j1.A, j1.X, j1.M, j1.part, j1.bias_part, j1.rows_per_block, j1.a, j1.dr, blockIdx.x - first1);
@@ -1548,11 +1554,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn256_jobs_kernel(TnJobs jobs) {
     tn256_body<X3, false, false>(ring, j.A, j.B, nullptr, 0, j.part, j.bias_part, nullptr, nullptr, j.M,
                                  j.rows_per_block, j.dir, blk, nblk);
   }
-}
-
-__global__ __launch_bounds__(256) void dir_enc_dw_kernel(mlp::FieldArgs a, DirFold dir, float* __restrict__ part,
-                                                         float* __restrict__ bias_part) {
-  dir_enc_dw_block(a, dir, part, bias_part, blockIdx.x);
 }
 
 // Deterministic column sums (bias gradients dPre^T 1) where no dW kernel folds them in:
@@ -2642,8 +2643,8 @@ int64_t tn_ws_floats(int64_t M, int N, int K) {
   return best;
 }
 
-// dW of an encoding layer (ENC 0: layer_xyz1 from dPre(xyz1), ENC 1: layer_dir1's view columns
-// from dPre(dir1)) with the encodings generated in the kernel; ws: the deterministic path
+// dW of an encoding layer (ENC 0: layer_xyz1 from dPre(xyz1), 3xbf16 only; ENC 1: layer_dir1's view
+// columns from dPre(dir1)) with the encodings generated in the kernel; ws: the deterministic path
 // (enc_ws_parts(M) * 256 * K floats).
 // about one round of two workgroups per CU: each workgroup's prologue (three geometry stages, two
 // DMA stages) and partial tile are paid half as often as with 1024 (r03k: 144.8 -> 135.3 us per
@@ -2655,8 +2656,9 @@ int64_t enc_rows(int64_t M) {
 int64_t enc_parts(int64_t M) { return ceil_div(M, enc_rows(M)); }
 
 int gemm_tn_enc(int enc, const float* A, const mlp::FieldArgs& a, float* C, int64_t ldc, hipStream_t st, bool x3,
-                float* ws, float* bias = nullptr, float* bias_ws = nullptr, Reducer* rd = nullptr,
-                grad::DirRole dr = {}) {
+                float* ws, float* bias = nullptr, float* bias_ws = nullptr, Reducer* rd = nullptr) {
+  // fp32 layer_xyz1 reads the forward's encoding plane or a given x_enc (train_bwd_xyz1), never this
+  if (enc == 0 && !x3) return CN_EUNSUPPORTED;
   const int64_t rows = enc_rows(a.m);
   const unsigned nb = static_cast<unsigned>(ceil_div(a.m, rows));
   const int K = enc == 0 ? 63 : 27;
@@ -2665,15 +2667,14 @@ int gemm_tn_enc(int enc, const float* A, const mlp::FieldArgs& a, float* C, int6
     if (bias) bias_ws = rd->take((int64_t)nb * 256);
   }
 #define CN_ENC(X3_, E_, M_) \
-  hipLaunchKernelGGL((grad::gemm_tn_enc_kernel<X3_, E_, M_>), dim3(nb + dr.n), dim3(512), 0, st, A, a, C, ldc, ws, \
-                     bias ? bias_ws : nullptr, rows, dr)
+  hipLaunchKernelGGL((grad::gemm_tn_enc_kernel<X3_, E_, M_>), dim3(nb), dim3(512), 0, st, A, a, C, ldc, ws, \
+                     bias ? bias_ws : nullptr, rows, grad::DirRole{})
   const bool pts = a.pts != nullptr;
   if (x3) {
     if (enc == 0) { if (pts) CN_ENC(true, 0, mlp::kFromPts); else CN_ENC(true, 0, mlp::kFromRayZ); }
     else { if (pts) CN_ENC(true, 1, mlp::kFromPts); else CN_ENC(true, 1, mlp::kFromRayZ); }
   } else {
-    if (enc == 0) { if (pts) CN_ENC(false, 0, mlp::kFromPts); else CN_ENC(false, 0, mlp::kFromRayZ); }
-    else { if (pts) CN_ENC(false, 1, mlp::kFromPts); else CN_ENC(false, 1, mlp::kFromRayZ); }
+    if (pts) CN_ENC(false, 1, mlp::kFromPts); else CN_ENC(false, 1, mlp::kFromRayZ);
   }
 #undef CN_ENC
   int rc = launch_status();
@@ -3011,7 +3012,7 @@ extern "C" int cn_ray_points_backward(const float* g_pts, const float* z, int64_
 // Every dW GEMM of one backward keeps its partial tiles until the single deferred reduction:
 // the sum of their slices (+ five column-sum partial blocks -- three biases, g_code's feat and xyz2
 // rows -- the small d raw column sums and the 64-float alignment of each take).
-// The DIRS fold's own slices (dir1_dw_folded, n_samples >= 32): gsum slots for <= 256 workgroups +
+// The DIRS fold's own slices (tn_batch_plan's kind-2 job, n_samples >= 32): gsum slots for <= 256 workgroups +
 // m / 512 direction groups, and the encoding / bias partials of those groups.
 static int64_t dirs_ws_floats(int64_t m) {
   const int64_t groups = ceil_div(m, 512);
@@ -3025,46 +3026,13 @@ static int64_t train_dw_ws_floats(int64_t m) {
          dirs_ws_floats(m);
 }
 
-// layer_dir1's dW (C: [feat | 27 view-encoding columns], ldc 283) and bias in one pass over its dPre
-// plane (the DIRS fold: gemm_tn256_kernel<false, false, true> + dir_enc_dw_kernel).  Needs the
-// whole-tile plan, whole direction groups (n_rays and the Q1 chunk multiples of 16) and at most
-// `budget` floats of reducer workspace; CN_EUNSUPPORTED otherwise, before anything is launched
-// (the caller then runs the [feat] GEMM and gemm_tn_enc separately).
-static int dir1_dw_folded(const float* dpre, const float* feat, float* C, float* bias, const mlp::FieldArgs& a,
-                          hipStream_t st, Reducer* rd, int64_t budget) {
-  const int64_t M = a.m;
-  const TnPlan pl = tn_plan(dpre, 256, feat, 256, M, 256, 256, false);
-  const int64_t rc = std::min(a.chunk_rows, a.n_rays);
-  if (pl.kind != kTn256 || a.n_rays % 16 || rc % 16 || a.n_samples < 32 || M * 1024 + 64 * 1024 >= (int64_t(1) << 32))
-    return CN_EUNSUPPORTED;
-  const int64_t total = M / 16, per = ceil_div(total, 256), nb = ceil_div(total, per), groups = a.n_rays / 16;
-  const int64_t nd = ceil_div(groups, grad::kDirGroups);
-  const int64_t need = (nb + groups) * 4096 + nb * 65536 + nd * 256 * 28 + 4 * 64;
-  if (nb > pl.parts || need > budget) return CN_EUNSUPPORTED;
-  grad::DirFold d{static_cast<unsigned>(a.n_rays), static_cast<unsigned>(a.n_samples),
-                  static_cast<unsigned>(rc), static_cast<unsigned>(per),
-                  static_cast<unsigned>(total), rd->take((nb + groups) * 4096)};
-  float* ws = rd->take(nb * 65536);
-  hipLaunchKernelGGL((grad::gemm_tn256_kernel<false, false, true>), dim3(static_cast<unsigned>(nb)), dim3(512), 0, st,
-                     dpre, feat, C, 283, ws, nullptr, nullptr, nullptr, M, 0, d);
-  CN_TRY(launch_status());
-  float* ep = rd->take(nd * 256 * 27);
-  float* bp = rd->take(nd * 256);
-  hipLaunchKernelGGL(grad::dir_enc_dw_kernel, dim3(static_cast<unsigned>(nd)), dim3(256), 0, st, a, d, ep, bp);
-  CN_TRY(launch_status());
-  CN_TRY(reduce(rd, ws, nb, 256, 256, C, 283, st));
-  CN_TRY(reduce(rd, ep, nd, 256, 27, C + 256, 283, st));
-  return reduce(rd, bp, nd, 1, 256, bias, 256, st);
-}
-
 // The whole-tile dW GEMMs of one training backward, queued and launched as ONE
 // gemm_tn256_jobs_kernel (TnJobs).  add() records a GEMM C += A^T B (+ its bias column sums, the
 // sigma row, the DIRS view-encoding fold); launch() splits the grid over the jobs in proportion to
 // their rows times their per-row cost, takes each job's partial tiles from the reducer and queues
 // the fixed-order sums (same partial order within a job: deterministic).  The costs belong to the
 // layer slot, not to the job's kind, so a job's split -- and its summation order -- does not depend
-// on whether another slot takes the DIRS fold.  CN_TN_JOBS=0 in the environment launches the GEMMs
-// one by one (A/B); CN_TN_COST="c0,c1,c2,c3,c4" overrides the slot costs.
+// on whether another slot takes the DIRS fold.
 struct TnBatch {
   struct Pending {
     const float* A;
@@ -3085,76 +3053,22 @@ struct TnBatch {
   int n = 0;
 };
 
-// CN_XENC_PLANE=0: layer_xyz1's dW regenerates the encodings (gemm_tn_enc_kernel) instead of reading the
-// forward's encoding plane (A/B)
-static bool xenc_plane_enabled() {
-  static const int on = [] {
-    const char* e = getenv("CN_XENC_PLANE");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
-
-// layer_xyz1's dW (the fp32 encoding-plane pass) as a job of the batched dW launch instead of its own
-// launch (the DIRS fold's per-direction pass then runs alone after it, on the launch's direction sums):
-// the batched launch grows by ~220 us per C3 chunk -- the pass is MFMA work (a quarter of a 256 x 256
-// GEMM's per row), not a stream that hides beside the GEMMs -- against ~237 us for its own launch and
-// fewer partial tiles to reduce (r06f: C3 39.14 / 39.19 -> 39.17 / 38.96 ms, 3080 13.77 / 13.80 ->
-// 13.63 / 13.60 ms at slot cost 0.3; 0.25 starves it: 42.7 ms; 0.4 takes CUs from the GEMMs).
-// CN_XENC_ROLE=0: its own launch (A/B).
-static bool xenc_role_enabled() {
-  static const int on = [] {
-    const char* e = getenv("CN_XENC_ROLE");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
-
-// CN_DIR_IN_ENC=0: the DIRS fold's dir_enc_dw pass as its own launch again (A/B; bitwise the same)
-static bool dir_in_enc_enabled() {
-  static const int on = [] {
-    const char* e = getenv("CN_DIR_IN_ENC");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
-
-// CN_FIELD_PAIR=0: a render's two fields' backward and dW launches one field after the other (A/B;
-// bitwise the same gradients)
-static bool pair_enabled() {
-  static const int on = [] {
-    const char* e = getenv("CN_FIELD_PAIR");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
-
-static bool tn_jobs_enabled() {
-  static const int on = [] {
-    const char* e = getenv("CN_TN_JOBS");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
-
 // The training backward's slot costs: layer_dir2, layer_dir1 (DIRS where it applies), fc_out
 // (SIG), layer_xyz2 -- r03 per-launch times 375.5, 387.6, 394.7, 375.5 us -- and the RGB pass: an
 // RGB workgroup streams ~40 GB/s of v2 beside the GEMMs (r03l: 6 of them, cost 0.1, held the
 // launch 1.70 ms; 4 (0.07) 2.5 ms; 8-9 (0.14) balanced; r03n: 0.15 / 0.18 / 0.24 gave 41.5 / 41.7 /
 // 41.7 ms per C3 iteration), 1 KiB per row, ~0.12 of a whole-tile row.  Kept a little above that:
 // a late RGB workgroup holds up the whole launch, a spare one costs 1/256 of it.
-static const float* tn_slot_cost() {
-  static float w[6] = {1.0f, 1.03f, 1.05f, 1.0f, 0.16f, 0.3f};
-  static const bool init = [] {
-    const char* e = getenv("CN_TN_COST");
-    if (e) sscanf(e, "%f,%f,%f,%f,%f,%f", &w[0], &w[1], &w[2], &w[3], &w[4], &w[5]);
-    return true;
-  }();
-  (void)init;
-  return w;
-}
+// The last slot is XENC: layer_xyz1's dW (the fp32 encoding-plane pass) as a job of the batched dW
+// launch instead of its own launch (the DIRS fold's per-direction pass then runs alone after it, on
+// the launch's direction sums): the batched launch grows by ~220 us per C3 chunk -- the pass is MFMA
+// work (a quarter of a 256 x 256 GEMM's per row), not a stream that hides beside the GEMMs -- against
+// ~237 us for its own launch and fewer partial tiles to reduce (r06f: C3 39.14 / 39.19 -> 39.17 /
+// 38.96 ms, 3080 13.77 / 13.80 -> 13.63 / 13.60 ms at slot cost 0.3; 0.25 starves it: 42.7 ms; 0.4
+// takes CUs from the GEMMs).
+constexpr float kTnSlotCost[6] = {1.0f, 1.03f, 1.05f, 1.0f, 0.16f, 0.3f};
 
-// DIRS fold applicability (dir1_dw_folded's conditions, without the workspace budget).
+// DIRS fold applicability.
 static bool dirs_foldable(const mlp::FieldArgs& a) {
   const int64_t rc = std::min(a.chunk_rows, a.n_rays);
   return a.n_rays % 16 == 0 && rc % 16 == 0 && a.n_samples >= 32 && a.m * 1024 + 64 * 1024 < (int64_t(1) << 32) &&
@@ -3227,10 +3141,10 @@ static int tn_jobs_launch(const grad::TnJobs& jobs, int grid, bool x3, hipStream
   return launch_status();
 }
 
-// After the launch: the fixed-order sums of every job's partials queued on the reducer (the DIRS job's
-// dir_enc_dw pass launched here, or -- dir_out set -- returned as a role for the next gemm_tn_enc /
-// gemm_tn_xenc launch; its partials' reductions are queued here either way).
-static int tn_batch_post(TnBatch& b, const grad::TnJobs& jobs, hipStream_t st, Reducer* rd, grad::DirRole* dir_out) {
+// After the launch: the fixed-order sums of every job's partials queued on the reducer.  The DIRS job's
+// dir_enc_dw pass is returned in dir_out as a role for the following gemm_tn_xenc launch (left as it
+// is without a kind-2 job); its partials' reductions are queued here.
+static int tn_batch_post(TnBatch& b, const grad::TnJobs& jobs, hipStream_t st, Reducer* rd, grad::DirRole& dir_out) {
   for (int k = 0; k < b.n; ++k) {
     const TnBatch::Pending& q = b.p[k];
     const grad::TnJob& j = jobs.j[k];
@@ -3238,13 +3152,7 @@ static int tn_batch_post(TnBatch& b, const grad::TnJobs& jobs, hipStream_t st, R
       const int64_t groups = q.a.n_rays / 16, nd = ceil_div(groups, grad::kDirGroups);
       float* ep = rd->take(nd * 256 * 27);
       float* bp = rd->take(nd * 256);
-      if (dir_out) {
-        *dir_out = grad::DirRole{j.dir, ep, bp, static_cast<unsigned>(nd)};
-      } else {
-        hipLaunchKernelGGL(grad::dir_enc_dw_kernel, dim3(static_cast<unsigned>(nd)), dim3(256), 0, st, q.a, j.dir, ep,
-                           bp);
-        CN_TRY(launch_status());
-      }
+      dir_out = grad::DirRole{j.dir, ep, bp, static_cast<unsigned>(nd)};
       CN_TRY(reduce(rd, j.part, j.n_blocks, 256, 256, q.C, q.ldc, st));
       CN_TRY(reduce(rd, ep, nd, 256, 27, q.C + 256, q.ldc, st));
       CN_TRY(reduce(rd, bp, nd, 1, 256, q.bias, 256, st));
@@ -3269,7 +3177,7 @@ static int tn_batch_post(TnBatch& b, const grad::TnJobs& jobs, hipStream_t st, R
   return CN_OK;
 }
 
-static int tn_batch_launch(TnBatch& b, bool x3, hipStream_t st, Reducer* rd, grad::DirRole* dir_out = nullptr) {
+static int tn_batch_launch(TnBatch& b, bool x3, hipStream_t st, Reducer* rd, grad::DirRole& dir_out) {
   if (b.n == 0) return CN_OK;
   grad::TnJobs jobs;
   const int grid = tn_batch_plan(b, rd, jobs);
@@ -3280,8 +3188,8 @@ static int tn_batch_launch(TnBatch& b, bool x3, hipStream_t st, Reducer* rd, gra
 // Two fields' batches (a render's coarse and fine backward) as ONE launch: each field's jobs keep the
 // split of their own launch (the same workgroup counts and rows, so the same partial tiles), field 1's
 // workgroups after field 0's -- they start on the CUs field 0's leave, filling its finish spread.
-static int tn_batch_launch2(TnBatch& b0, Reducer* r0, grad::DirRole* d0, TnBatch& b1, Reducer* r1,
-                            grad::DirRole* d1, bool x3, hipStream_t st) {
+static int tn_batch_launch2(TnBatch& b0, Reducer* r0, grad::DirRole& d0, TnBatch& b1, Reducer* r1,
+                            grad::DirRole& d1, bool x3, hipStream_t st) {
   if (b0.n == 0 || b1.n == 0 || b0.n + b1.n > grad::kMaxTnJobs) {
     CN_TRY(tn_batch_launch(b0, x3, st, r0, d0));
     return tn_batch_launch(b1, x3, st, r1, d1);
@@ -3427,8 +3335,8 @@ extern "C" int cn_field_backward_fused_multi(int fmt_t, const cn_field_fused_bwd
   }
   const cn_field_fused_bwd &f0 = fields[0], &f1 = fields[1];
   CN_CHECK_ARG(!d_rd_between || (f0.d_rd && f0.d_rd == f1.d_rd && f0.n_rays == f1.n_rays));
-  bool pair = fmt_t == CN_FMT_F32_W16_T && pair_enabled() && f0.n_rays == f1.n_rays && f0.d_ro == f1.d_ro &&
-              f0.d_rd == f1.d_rd && !f0.pts && !f1.pts && !f0.d_pts && !f1.d_pts;
+  bool pair = fmt_t == CN_FMT_F32_W16_T && f0.n_rays == f1.n_rays && f0.d_ro == f1.d_ro && f0.d_rd == f1.d_rd &&
+              !f0.pts && !f1.pts && !f0.d_pts && !f1.d_pts;
   for (const cn_field_fused_bwd* f : {&f0, &f1})
     pair = pair && f->workspace && f->n_codes == 1 && f->n_samples % 16 == 0 && f->ro && f->z;
   mlp::FieldArgs a[2];
@@ -3516,7 +3424,7 @@ extern "C" int cn_field_backward_train(const float* packed_t, const float* const
 // stages so that a render's two fields can share their launches (cn_field_backward_train_multi).
 struct TrainBwd {
   bool x3 = false, wg = false, fold_code = false, jobs = false, rgb_role = false, dual_code = false, dirs = false;
-  bool xenc_job = false;   // layer_xyz1's dW rides in the batched launch (CN_XENC_ROLE=1)
+  bool xenc_job = false;   // layer_xyz1's dW rides in the batched launch
   int mode = 0;
   mlp::FieldArgs a = {};
   const float* saved = nullptr;
@@ -3528,11 +3436,11 @@ struct TrainBwd {
   const float* P[5] = {};
   Reducer red = {};
   TnBatch tb;
-  grad::DirRole dir_role = {};
+  grad::DirRole dir_role = {};   // the DIRS job's per-direction pass, a role of layer_xyz1's launch (tn_batch_post)
 };
 
 // layer_xyz1's dW reads the fp32 forward's own encodings (saved's encoding plane)
-static bool train_bwd_xenc(const TrainBwd& t) { return !t.x_enc && !t.x3 && xenc_plane_enabled(); }
+static bool train_bwd_xenc(const TrainBwd& t) { return !t.x_enc && !t.x3; }
 
 static int train_bwd_setup(int fmt_t, const cn_field_train_bwd& f, TrainBwd& t) {
   using namespace mlp;
@@ -3591,13 +3499,13 @@ static int train_bwd_setup(int fmt_t, const cn_field_train_bwd& f, TrainBwd& t) 
   if (t.fold_code) a.g_code = nullptr;
   for (int k = 0; k < 5; ++k) t.P[k] = f.workspace + k * M * 256;
   t.red = Reducer{nullptr, f.workspace + 5 * M * 256, {}, 0};
-  t.jobs = tn_jobs_enabled() && M >= 64 * 1024;
+  t.jobs = M >= 64 * 1024;
   // fc_rgb (h half): dW += d rgb^T v2 (+ g_code's rgb / sigma entries, folded, in the same pass); as the
   // batched launch's RGB role where that runs (fp32, folded code)
   t.rgb_role = t.jobs && t.fold_code && !t.x3;
   t.dual_code = t.rgb_role;  // the g_code sums also land in the bias gradients (below)
   t.dirs = t.jobs && !t.x3 && !t.x_enc && dirs_foldable(a);
-  t.xenc_job = t.jobs && t.wg && train_bwd_xenc(t) && xenc_role_enabled();
+  t.xenc_job = t.jobs && t.wg && train_bwd_xenc(t);
   return CN_OK;
 }
 
@@ -3619,8 +3527,6 @@ static int train_bwd_queue(TrainBwd& t, hipStream_t st) {
   }
   float* const gc_feat = t.fold_code ? t.g_code + kCbFeat : nullptr;
   float* const gc_xyz2 = t.fold_code ? t.g_code + kCbXyz2 : nullptr;
-  float* const ws = nullptr;
-  float* const bws = nullptr;
   Reducer* red = &t.red;
   const float* const* P = t.P;
   const float* h1 = t.saved;
@@ -3633,7 +3539,7 @@ static int train_bwd_queue(TrainBwd& t, hipStream_t st) {
   } else if (t.fold_code) {
     CN_TRY(rgb_dw_draw_sums(t.d_raw, v2, G(kWRgb), 512, M, t.g_code + kCbRgb, t.g_code + kCbSigma, st, red));
   } else {
-    CN_TRY(gemm_tn(t.d_raw, 4, v2, 256, G(kWRgb), 512, M, 3, 256, st, x3, ws, nullptr, nullptr, red));
+    CN_TRY(gemm_tn(t.d_raw, 4, v2, 256, G(kWRgb), 512, M, 3, 256, st, x3, nullptr, nullptr, nullptr, red));
   }
   if (t.jobs) {
     // the four 256 x 256 layers as ONE whole-tile launch (TnBatch): layer_dir2, layer_dir1 [feat]
@@ -3641,7 +3547,7 @@ static int train_bwd_queue(TrainBwd& t, hipStream_t st) {
     // layer_xyz2
     TnBatch& tb = t.tb;
     tb.n = 0;
-    const float* c = tn_slot_cost();
+    const float* c = kTnSlotCost;
     // with one code row the g_code entries summed here ARE the bias gradients of layer_xyz2, fc_out
     // and fc_rgb (gcode_bias_kernel's column sums over one row): the reductions add each sum to both
     // (bias2 / sig2), bitwise gcode_bias_kernel's 0 + g then b + that, and that launch is not needed
@@ -3661,30 +3567,18 @@ static int train_bwd_queue(TrainBwd& t, hipStream_t st) {
     return CN_OK;
   }
   // layer_dir2
-  CN_TRY(gemm_tn(P[0], 256, v1, 256, G(kWDir2), 256, M, 256, 256, st, x3, ws, B(kBDir2), bws, red));
+  CN_TRY(gemm_tn(P[0], 256, v1, 256, G(kWDir2), 256, M, 256, 256, st, x3, nullptr, B(kBDir2), nullptr, red));
   // layer_dir1: [feat | dir enc]
-  const int64_t dir1_budget =
-      tn_ws_floats(M, 256, 256) + std::max(tn_ws_floats(M, 256, 27), enc_parts(M) * 256 * 27) + dirs_ws_floats(M);
-  const int folded = x3 || t.x_enc ? CN_EUNSUPPORTED
-                                   : dir1_dw_folded(P[1], feat, G(kWDir1), B(kBDir1), t.a, st, red, dir1_budget);
-  if (folded != CN_OK) {
-    if (folded != CN_EUNSUPPORTED) return folded;
-    CN_TRY(gemm_tn(P[1], 256, feat, 256, G(kWDir1), 283, M, 256, 256, st, x3, ws, B(kBDir1), bws, red));
-    if (t.x_enc)
-      CN_TRY(gemm_tn(P[1], 256, t.x_enc + 63, 90, G(kWDir1) + 256, 283, M, 256, 27, st, x3, ws, nullptr, nullptr, red));
-    else CN_TRY(gemm_tn_enc(1, P[1], t.a, G(kWDir1) + 256, 283, st, x3, ws, nullptr, nullptr, red));
-  }
+  CN_TRY(gemm_tn(P[1], 256, feat, 256, G(kWDir1), 283, M, 256, 256, st, x3, nullptr, B(kBDir1), nullptr, red));
+  if (t.x_enc)
+    CN_TRY(gemm_tn(P[1], 256, t.x_enc + 63, 90, G(kWDir1) + 256, 283, M, 256, 27, st, x3, nullptr, nullptr, nullptr,
+                   red));
+  else CN_TRY(gemm_tn_enc(1, P[1], t.a, G(kWDir1) + 256, 283, st, x3, nullptr, nullptr, nullptr, red));
   // fc_out (h half): row 0 from d sigma, rows 1.. from d feat
-  CN_TRY(gemm_tn(P[2], 256, h2, 256, G(kWOut) + 512, 512, M, 256, 256, st, x3, ws, gc_feat, bws, red, t.d_raw + 3,
-                 G(kWOut)));
+  CN_TRY(gemm_tn(P[2], 256, h2, 256, G(kWOut) + 512, 512, M, 256, 256, st, x3, nullptr, gc_feat, nullptr, red,
+                 t.d_raw + 3, G(kWOut)));
   // layer_xyz2 (h half)
-  return gemm_tn(P[3], 256, h1, 256, G(kWXyz2), 512, M, 256, 256, st, x3, ws, gc_xyz2, bws, red);
-}
-
-// The DIRS fold's per-direction pass rides in layer_xyz1's encoding dW launch when that is a gemm_tn_enc /
-// gemm_tn_xenc launch: one launch fewer per field and chunk.
-static grad::DirRole* train_bwd_dir_out(TrainBwd& t) {
-  return t.jobs && t.dirs && !t.x_enc && dir_in_enc_enabled() ? &t.dir_role : nullptr;
+  return gemm_tn(P[3], 256, h1, 256, G(kWXyz2), 512, M, 256, 256, st, x3, nullptr, gc_xyz2, nullptr, red);
 }
 
 // After the batched launch: layer_dir1's view columns where the DIRS fold did not take them.
@@ -3697,8 +3591,8 @@ static int train_bwd_after_jobs(TrainBwd& t, hipStream_t st) {
 }
 
 
-// layer_xyz1 (its own launch: as a role of the batched launch it ran no faster per CU -- it is compute
-// work, not a bandwidth pass that could hide beside the GEMMs; r03m)
+// layer_xyz1's dW as its own launch where it is no job of the batched launch (3xbf16, x_enc given, no
+// batched plan); where it is one, the DIRS fold's per-direction pass alone.
 static int train_bwd_xyz1(TrainBwd& t, hipStream_t st) {
   using namespace mlp;
   float* C = t.grads[kWXyz1];
@@ -3712,40 +3606,18 @@ static int train_bwd_xyz1(TrainBwd& t, hipStream_t st) {
   if (t.x_enc)
     return gemm_tn(t.P[4], 256, t.x_enc, 90, C, 63, t.a.m, 256, 63, st, t.x3, nullptr, bias, nullptr, &t.red);
   if (train_bwd_xenc(t)) return gemm_tn_xenc(t.P[4], t.saved + 5 * t.a.m * 256, t.a, C, 63, st, bias, &t.red, t.dir_role);
-  return gemm_tn_enc(0, t.P[4], t.a, C, 63, st, t.x3, nullptr, bias, nullptr, &t.red, t.dir_role);
+  return gemm_tn_enc(0, t.P[4], t.a, C, 63, st, t.x3, nullptr, bias, nullptr, &t.red);
 }
 
-// Two fields' layer_xyz1 dW passes (gemm_tn_xenc each) as one gemm_tn_xenc2_kernel launch.
+// A pair's layer_xyz1 launch: both fields' dW ran as XENC jobs of the batched launch (a pair has
+// xenc_job set for both), so this is their DIRS fold's per-direction passes in one gemm_tn_xenc2_kernel.
 static int train_bwd_xyz1_pair(TrainBwd& t0, TrainBwd& t1, hipStream_t st) {
-  using namespace mlp;
-  grad::XencJob j[2];
-  TrainBwd* t[2] = {&t0, &t1};
-  unsigned blocks[2];
-  if (t0.xenc_job && t1.xenc_job) {   // their dW ran in the batched launch: the DIRS passes alone
-    for (int f = 0; f < 2; ++f) {
-      j[f] = grad::XencJob{nullptr, nullptr, 0, nullptr, nullptr, 0, t[f]->a, t[f]->dir_role};
-      blocks[f] = t[f]->dir_role.n;
-    }
-    if (blocks[0] + blocks[1] == 0) return CN_OK;
-    hipLaunchKernelGGL(grad::gemm_tn_xenc2_kernel, dim3(blocks[0] + blocks[1]), dim3(512), 0, st, j[0], j[1], blocks[0]);
-    return launch_status();
-  }
-  for (int f = 0; f < 2; ++f) {
-    const int64_t m = t[f]->a.m, rows = enc_rows(m);
-    const unsigned nb = static_cast<unsigned>(ceil_div(m, rows));
-    float* bias = t[f]->grads[kBXyz1];
-    j[f] = grad::XencJob{t[f]->P[4], t[f]->saved + 5 * m * 256, m, t[f]->red.take((int64_t)nb * 256 * 63),
-                         bias ? t[f]->red.take((int64_t)nb * 256) : nullptr, rows, t[f]->a, t[f]->dir_role};
-    blocks[f] = nb + t[f]->dir_role.n;
-  }
-  hipLaunchKernelGGL(grad::gemm_tn_xenc2_kernel, dim3(blocks[0] + blocks[1]), dim3(512), 0, st, j[0], j[1], blocks[0]);
-  CN_TRY(launch_status());
-  for (int f = 0; f < 2; ++f) {
-    const unsigned nb = blocks[f] - t[f]->dir_role.n;
-    CN_TRY(reduce(&t[f]->red, j[f].part, nb, 256, 63, t[f]->grads[kWXyz1], 63, st));
-    if (j[f].bias_part) CN_TRY(reduce(&t[f]->red, j[f].bias_part, nb, 1, 256, t[f]->grads[kBXyz1], 256, st));
-  }
-  return CN_OK;
+  const grad::XencJob j0{nullptr, nullptr, 0, nullptr, nullptr, 0, t0.a, t0.dir_role};
+  const grad::XencJob j1{nullptr, nullptr, 0, nullptr, nullptr, 0, t1.a, t1.dir_role};
+  if (t0.dir_role.n + t1.dir_role.n == 0) return CN_OK;
+  hipLaunchKernelGGL(grad::gemm_tn_xenc2_kernel, dim3(t0.dir_role.n + t1.dir_role.n), dim3(512), 0, st, j0, j1,
+                     t0.dir_role.n);
+  return launch_status();
 }
 
 // After the deferred reduction: the biases formed from a folded g_code where no reduction did it.
@@ -3767,7 +3639,7 @@ static int train_bwd_one(TrainBwd& t, hipStream_t st) {
   CN_TRY(train_bwd_dx(t, st));
   if (!t.wg) return CN_OK;
   CN_TRY(train_bwd_queue(t, st));
-  if (t.jobs) CN_TRY(tn_batch_launch(t.tb, t.x3, st, &t.red, train_bwd_dir_out(t)));
+  if (t.jobs) CN_TRY(tn_batch_launch(t.tb, t.x3, st, &t.red, t.dir_role));
   CN_TRY(train_bwd_after_jobs(t, st));
   CN_TRY(train_bwd_xyz1(t, st));
   CN_TRY(t.red.flush());
@@ -3799,7 +3671,7 @@ extern "C" int cn_field_backward_train_multi(int fmt_t, const cn_field_train_bwd
   hipStream_t st = as_stream(stream);
   TrainBwd t[2];
   for (int k = 0; k < n_fields; ++k) CN_TRY(train_bwd_setup(fmt_t, fields[k], t[k]));
-  bool pair = n_fields == 2 && !t[0].x3 && pair_enabled();
+  bool pair = n_fields == 2 && !t[0].x3;
   for (int k = 0; pair && k < 2; ++k)
     pair = t[k].wg && t[k].jobs && t[k].mode == mlp::kFromRayZ && train_bwd_xenc(t[k]);
   if (pair) {
@@ -3813,8 +3685,7 @@ extern "C" int cn_field_backward_train_multi(int fmt_t, const cn_field_train_bwd
   }
   CN_TRY(train_bwd_queue(t[0], st));
   CN_TRY(train_bwd_queue(t[1], st));
-  CN_TRY(tn_batch_launch2(t[0].tb, &t[0].red, train_bwd_dir_out(t[0]), t[1].tb, &t[1].red, train_bwd_dir_out(t[1]),
-                          false, st));
+  CN_TRY(tn_batch_launch2(t[0].tb, &t[0].red, t[0].dir_role, t[1].tb, &t[1].red, t[1].dir_role, false, st));
   CN_TRY(train_bwd_after_jobs(t[0], st));
   CN_TRY(train_bwd_after_jobs(t[1], st));
   CN_TRY(train_bwd_xyz1_pair(t[0], t[1], st));

@@ -335,8 +335,6 @@ int fused_backward_args(int fmt_t, const float* packed_t, const uint32_t* masks,
                         int64_t n_samples, int64_t chunk_rows, const int64_t* code_index, int64_t n_codes,
                         const float* freqs_xyz, const float* freqs_dir, float* g_code, float* d_pts, float* d_ro,
                         float* d_rd, FieldArgs& a);
-// The training backwards' no-geometry schedule (no d ro / d rd / d pts wanted) unless CN_BWD_NOGEO=0.
-bool nogeo_enabled();
 
 // 3xbf16 16x16x32 two-waves-per-SIMD variant (mlp_x3w.hip): inference forward only.
 int64_t packed_floats_x3w();

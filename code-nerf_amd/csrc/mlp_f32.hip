@@ -1910,16 +1910,6 @@ int launch_pack_w16t(const Params& P, float* packed, hipStream_t st) {
   return cn::launch_status();
 }
 
-// CN_BWD_NOGEO=0 keeps the geometry schedule in training too (A/B timing; the weight and code
-// gradients are bitwise the same either way)
-bool nogeo_enabled() {
-  static const int on = [] {
-    const char* e = getenv("CN_BWD_NOGEO");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return on != 0;
-}
-
 static unsigned bwd_grid_w16(const FieldArgs& a) {
   return static_cast<unsigned>(
       std::min<int64_t>(std::min<int64_t>(cn::ceil_div(a.m, w16::kTile), cu_count_w16()), kMaxBwdBlocks));
@@ -1929,7 +1919,7 @@ static unsigned bwd_grid_w16(const FieldArgs& a) {
 // (the same mode, training / no-geometry / deterministic choice), else CN_EUNSUPPORTED before any launch.
 int launch_field_w16_bwd2(int mode, FieldArgs& a0, FieldArgs& a1, hipStream_t st) {
   auto form = [](const FieldArgs& a) {
-    if (a.dpre) return (!a.d_pts && !a.d_ro && !a.d_rd && nogeo_enabled()) ? 2 : 1;
+    if (a.dpre) return (!a.d_pts && !a.d_ro && !a.d_rd) ? 2 : 1;
     return a.gc_part ? 3 : 0;
   };
   const int f = form(a0);
@@ -1953,7 +1943,7 @@ int launch_field_w16_bwd(int mode, FieldArgs& a, hipStream_t st) {
   a.n_blocks = grid;
   const dim3 b(w16::kThreads);
   // training with no geometry gradient wanted (train.py: the rays are data): the 33-chunk schedule
-  if (a.dpre && !a.d_pts && !a.d_ro && !a.d_rd && nogeo_enabled()) {
+  if (a.dpre && !a.d_pts && !a.d_ro && !a.d_rd) {
     if (mode == kFromPts) hipLaunchKernelGGL((w16::field_w16_bwd_kernel<kFromPts, true, true>), dim3(grid), b, 0, st, a);
     else if (mode == kFromRayZ) hipLaunchKernelGGL((w16::field_w16_bwd_kernel<kFromRayZ, true, true>), dim3(grid), b, 0, st, a);
     else return CN_EUNSUPPORTED;

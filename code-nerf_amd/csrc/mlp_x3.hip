@@ -1536,7 +1536,7 @@ int launch_field_x3_bwd(int mode, FieldArgs& a, hipStream_t st) {
   const unsigned grid = static_cast<unsigned>(
       std::min<int64_t>(std::min<int64_t>(cn::ceil_div(a.m, x3::kTile), cu_count()), kMaxBwdBlocks));
   a.n_blocks = grid;
-  if (a.dpre && !a.d_pts && !a.d_ro && !a.d_rd && nogeo_enabled()) {
+  if (a.dpre && !a.d_pts && !a.d_ro && !a.d_rd) {   // training, no geometry gradient wanted
     switch (mode) {
       case kFromPts: hipLaunchKernelGGL((x3::field_x3_bwd_kernel<kFromPts, true, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
       case kFromRayZ: hipLaunchKernelGGL((x3::field_x3_bwd_kernel<kFromRayZ, true, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;

@@ -65,6 +65,35 @@ def test_argument_errors_need_no_gpu(lib_path):
         == _lib.CN_EINVAL
 
 
+def test_multi_entries_refuse_bad_job_arrays(lib_path):
+    """The render-pair entries check their job array and count on the host before any HIP call: a null
+    array and a count of 0 or 3 are CN_EINVAL, and so is a gradient between the fields with one field."""
+    from codenerf import _lib
+    lib = _lib.load(lib_path)
+    f32 = _lib.CN_FMT_F32_W16_T
+    train, fused, act = (_lib.FieldTrainBwd * 3)(), (_lib.FieldFusedBwd * 3)(), (_lib.CodeActJob * 3)()
+    z = ctypes.cast((ctypes.c_float * 256)(), ctypes.c_void_p)   # any non-null host pointer: never read
+    assert lib.cn_field_backward_train_multi(f32, None, 1, None) == _lib.CN_EINVAL
+    assert lib.cn_field_backward_fused_multi(f32, None, 1, None, None) == _lib.CN_EINVAL
+    assert lib.cn_code_bias_backward_act_multi(None, 1, z, z, 1, None) == _lib.CN_EINVAL
+    for n in (0, 3):
+        assert lib.cn_field_backward_train_multi(f32, train, n, None) == _lib.CN_EINVAL, n
+        assert lib.cn_field_backward_fused_multi(f32, fused, n, None, None) == _lib.CN_EINVAL, n
+        assert lib.cn_code_bias_backward_act_multi(act, n, z, z, 1, None) == _lib.CN_EINVAL, n
+    assert lib.cn_field_backward_fused_multi(f32, fused, 1, z, None) == _lib.CN_EINVAL
+
+
+def test_train_backward_workspace_is_pinned(lib_path):
+    """cn_field_backward_train_workspace_floats is ABI: callers size their buffers by it.  The values are
+    those of commit 2eda9be, the last one before the training backward's launch-plan switches and the
+    stand-alone DIRS fold were removed (the fold's slices stay part of the size)."""
+    from codenerf import _lib
+    lib = _lib.load(lib_path)
+    want = {1: 2663936, 8192: 33249024, 65536: 167646976, 70400: 170524928, 393216: 594286336}
+    for m, floats in want.items():
+        assert lib.cn_field_backward_train_workspace_floats(m) == floats, m
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from codenerf import ops

@@ -545,10 +545,11 @@ def test_test_time_optimize_runs(dev):
 @pytest.mark.parametrize("precision", ["f32", "bf16x3"])
 @pytest.mark.parametrize("mode,far", [("rayz", False), ("pts", False), ("pts", True), ("rayz", True)])
 def test_field_backward_train_generated_encodings(dev, mode, far, precision):
-    """The fused training backward's encoding-layer dW (layer_xyz1, layer_dir1's view columns) with
-    the encodings generated inside the dW kernel (x_enc None, the training path) matches the
-    x_enc-plane GEMMs at GEMM_TOL; every other gradient is the same deterministic computation and
-    must agree bit for bit.  Run twice: the generated path is bitwise reproducible.  ``far``: samples
+    """The fused training backward's encoding-layer dW (layer_xyz1, layer_dir1's view columns) without
+    x_enc (the training path: layer_dir1's view encodings generated inside the dW kernel; layer_xyz1's
+    read from the forward's saved encoding plane in fp32 and generated in the dW kernel in 3xbf16)
+    matches the x_enc-plane GEMMs at GEMM_TOL; every other gradient is the same deterministic computation
+    and must agree bit for bit.  Run twice: the path without x_enc is bitwise reproducible.  ``far``: samples
     past fast_sincosf's argument bound (pts: ONE sample of one 16-sample wave -- a mixed wave, which
     the fp32 forward and its dW kernel evaluate with sincosf throughout; rayz: one far ray), so both
     per-stage choices of the dW kernel run."""
@@ -603,11 +604,12 @@ def test_field_backward_train_generated_encodings(dev, mode, far, precision):
                                              ("rayz", 1050, 64, 256)])  # n_rays % 16 != 0: unfolded path
 def test_field_backward_train_dir1_fold(dev, mode, r, s, chunk):
     """At M >= 65536 (fp32) layer_dir1's view-encoding dW and bias come from per-direction column
-    sums of its dPre plane taken during the [feat] pass (gemm_tn256_kernel DIRS +
-    dir_enc_dw_kernel): the Q1 map makes rows j rcnt + d of a chunk share direction d.  Checked
+    sums of its dPre plane taken during the [feat] pass (the DIRS job of gemm_tn256_jobs_kernel, then
+    dir_enc_dw_block as a role of the gemm_tn_xenc_kernel launch): the Q1 map makes rows j rcnt + d of
+    a chunk share direction d.  Checked
     against the x_enc-plane GEMMs (the encodings as the forward made them) at GEMM_TOL; every other
-    gradient is the same products, at fp32 rounding: with generated encodings layer_xyz1's dW joins the
-    batched dW launch (grad.hip xenc_role_enabled), whose split of rows over the jobs -- so the other
+    gradient is the same products, at fp32 rounding: without x_enc layer_xyz1's dW joins the
+    batched dW launch (grad.hip TrainBwd::xenc_job), whose split of rows over the jobs -- so the other
     weights' partial-tile grouping -- follows its job list; two runs are bitwise identical."""
     from codenerf import ops, synthetic
     m = model(dev, 0)

@@ -177,3 +177,20 @@ def test_prep_plan_modes():
     assert A._prep_plan(meta, 1, 0, train) == (None, 0)
     meta_v1 = A._FieldMeta(64, 4096, [1.0] * 10, [1.0] * 4, precision="f32_v1", train_precision="f32")
     assert A._prep_plan(meta_v1, 1, 4096, train) == (None, 0)
+
+
+def test_library_sources_read_no_environment():
+    """The library's behaviour does not depend on the environment of the box: no source under csrc/ or
+    include/ calls getenv (an A/B is made against a variant library, not an environment switch).  The
+    build directory holds compiler output, not sources."""
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    found, seen = [], 0
+    for top in (os.path.join(root, "code-nerf_amd", "csrc"), os.path.join(root, "include")):
+        for d, dirs, files in os.walk(top):
+            dirs[:] = [x for x in dirs if not x.startswith("build")]
+            for f in files:
+                seen += 1
+                if b"getenv" in open(os.path.join(d, f), "rb").read():
+                    found.append(os.path.relpath(os.path.join(d, f), root))
+    assert seen > 10 and not found, found
