@@ -25,7 +25,7 @@ from .volumetric_render import volume_render
 
 __all__ = ["RaySampler", "PointSampler", "PositionalEmbedder", "volume_render", "prepare_samplers",
            "prepare_embedders", "predict_radiance_and_render", "forward_pass", "parallel_image_render",
-           "render_rays", "gather_rows", "gather_views", "density", "density_grid", "OccupancyGrid"]
+           "render_rays", "gather_rows", "gather_views", "density", "density_grid", "OccupancyGrid", "Mesh", "extract_mesh"]
 
 
 def prepare_samplers(cfg, height: int, width: int, intrinsics, datatype, device) -> Tuple[RaySampler, PointSampler]:
@@ -164,6 +164,64 @@ def density_grid(model, embedders, z_s: torch.Tensor, resolution: int, bound: fl
         if activated:
             out = torch.nn.functional.softplus(out - 1.0)
     return out.view(d, d, d)
+
+
+class Mesh:
+    """A triangle mesh: ``vertices`` (V, 3) float32 and ``faces`` (T, 3) int32 (0-based vertex ids,
+    counter-clockwise seen from outside), on any device.  Saving copies them to the host."""
+
+    def __init__(self, vertices: torch.Tensor, faces: torch.Tensor):
+        if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+            raise ValueError(f"vertices must be (V, 3) float32, got {tuple(vertices.shape)} {vertices.dtype}")
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+            raise ValueError(f"faces must be (T, 3) int32, got {tuple(faces.shape)} {faces.dtype}")
+        self.vertices, self.faces = vertices, faces
+
+    @property
+    def n_vertices(self) -> int:
+        return int(self.vertices.shape[0])
+
+    @property
+    def n_faces(self) -> int:
+        return int(self.faces.shape[0])
+
+    def _host(self):
+        return (self.vertices.detach().cpu().contiguous().numpy(), self.faces.detach().cpu().contiguous().numpy())
+
+    def save_obj(self, path: str) -> None:
+        """Wavefront OBJ text: ``v x y z`` (%.9g, which round-trips a float32) and ``f a b c``, 1-based."""
+        v, f = self._host()
+        with open(path, "w") as out:
+            out.writelines("v %.9g %.9g %.9g\n" % (float(x), float(y), float(z)) for x, y, z in v)
+            out.writelines("f %d %d %d\n" % (a + 1, b + 1, c + 1) for a, b, c in f.tolist())
+
+    def save_ply(self, path: str) -> None:
+        """Binary little-endian PLY: float32 x, y, z per vertex; a uchar count (3) and int32 indices per face."""
+        import numpy as np
+        v, f = self._host()
+        header = ("ply\nformat binary_little_endian 1.0\n"
+                  f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n"
+                  f"element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
+        rows = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+        rows["n"], rows["i"] = 3, f
+        with open(path, "wb") as out:
+            out.write(header.encode("ascii"))
+            out.write(v.astype("<f4").tobytes())
+            out.write(rows.tobytes())
+
+
+def extract_mesh(model, embedders, z_s: torch.Tensor, resolution: int, bound: float, level: float,
+                 activated: bool = True, max_points: int = 1 << 22) -> Mesh:
+    """The ``level`` iso-surface of one shape code's density as a triangle mesh, on the device:
+    density_grid(resolution, bound, activated, max_points) followed by ops.isosurface with that grid's
+    own ``linspace(-bound, bound, resolution)``, so every vertex lies on an edge of the sampled lattice.
+    ``level`` is in the grid's unit (activated density, or sigma_raw) and has no default; normals point
+    towards lower density.  Inference only; reads the vertex and face counts back once (a host
+    synchronisation, see ops.isosurface).  No vertex normals, simplification or colours."""
+    d = int(resolution)
+    nodes = density_grid(model, embedders, z_s, d, bound, activated=activated, max_points=max_points)
+    lin = torch.linspace(-bound, bound, d, dtype=torch.float32, device=nodes.device)
+    return Mesh(*ops.isosurface(nodes, level, lin))
 
 
 class OccupancyGrid:

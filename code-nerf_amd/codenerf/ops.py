@@ -609,6 +609,46 @@ def occupancy_expand(raw_compact: Optional[Tensor], state) -> Tensor:
     return raw
 
 
+# ------------------------------------------------------------------ iso-surface extraction
+
+
+def isosurface(nodes: Tensor, iso: float, axis: Tensor) -> Tuple[Tensor, Tensor]:
+    """The ``iso`` level set of a node grid as a triangle mesh (cn_isosurface_count / cn_isosurface_emit;
+    include/codenerf.h states the semantics): ``nodes`` (N, N, N), axis order [ix, iy, iz] -- what
+    nerf.density_grid returns -- and ``axis`` (N,) node coordinates, used on all three axes ->
+    (vertices (V, 3) float32, faces (T, 3) int32).  Marching tetrahedra on the Kuhn split of each cell:
+    one vertex per sign-changing edge in ascending (node, direction) order, faces in ascending (cell,
+    tetrahedron, triangle) order with normals towards the lower values; a node is inside iff its value
+    is > ``iso``.  Deterministic, no atomics.
+
+    The two totals are read back once (``.item()``) between the count and the emit: a HOST
+    SYNCHRONISATION, since the outputs are allocated to exactly that size.  With V = 0 both results are
+    empty and nothing is emitted."""
+    lib = _lib_ready()
+    nodes, axis = _cuda(nodes, "nodes"), _cuda(axis, "axis")
+    assert nodes.dim() == 3 and nodes.shape[0] == nodes.shape[1] == nodes.shape[2], "nodes must be (N, N, N)"
+    n = nodes.shape[0]
+    assert axis.shape == (n,), "axis must be (N,)"
+    iso = float(iso)
+    if iso != iso or iso in (float("inf"), float("-inf")):
+        raise ValueError(f"isosurface: iso must be finite (got {iso})")
+    ws_bytes = lib.cn_isosurface_workspace_bytes(n)
+    if ws_bytes < 0:
+        raise ValueError(f"isosurface: N = {n} is outside 2..513")
+    dev = nodes.device
+    workspace = torch.empty((ws_bytes + 7) // 8, device=dev, dtype=torch.int64)
+    counts = torch.empty(2, device=dev, dtype=torch.int64)
+    st = stream_of(nodes)
+    check(lib.cn_isosurface_count(ptr(nodes), n, iso, ptr(workspace), ptr(counts), st), "cn_isosurface_count")
+    n_vertices, n_faces = (int(k) for k in counts.tolist())       # host synchronisation (see the docstring)
+    vertices = torch.empty(n_vertices, 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(n_faces, 3, device=dev, dtype=torch.int32)
+    if n_vertices:
+        check(lib.cn_isosurface_emit(ptr(nodes), ptr(axis), n, iso, ptr(workspace), n_vertices, n_faces,
+                                     ptr(vertices), ptr(faces) if n_faces else None, st), "cn_isosurface_emit")
+    return vertices, faces
+
+
 # ------------------------------------------------------------------ weight-bounded colour culling
 
 

@@ -403,6 +403,67 @@ int cn_weight_cull(const float* weights, const float* ro, const float* rd, const
 int cn_scatter_rgb(const float* raw_compact, const int32_t* sample_index, int64_t n_rows, float* raw,
                    int64_t n_slots, cn_stream_t stream);
 
+/* --- Iso-surface extraction (inference) ---------------------------------
+ * A node grid to a triangle mesh, on the device: marching tetrahedra on the Kuhn (Freudenthal) split
+ * of each cell.  The split is the same in every cell, so neighbouring cells agree on every shared
+ * face diagonal and the surface is closed wherever it does not leave the grid; there are no
+ * ambiguous cases.
+ * Input: nodes (n, n, n) fp32, axis order [ix, iy, iz], node a = (ix, iy, iz) at linear index
+ * (ix n + iy) n + iz (what density_grid leaves); axis: n fp32 node coordinates, used on all three
+ * axes; iso: the level, finite; 2 <= n <= 513.
+ * Inside: a node is inside iff nodes[a] > iso -- a NaN and a value equal to iso are outside.
+ * Corners and edges: cube corner k in 0..7 of the cell with lower node p is p + off(k), off(k) =
+ * ((k >> 2) & 1, (k >> 1) & 1, k & 1) (x the most significant bit).  Every edge of the split runs
+ * from a node a to a + off(k), k in 1..7: direction d = k - 1, owned by its lower node a.  Edge (a, d)
+ * exists iff a + off(d + 1) is a node, and is active iff it exists and exactly one end is inside.
+ * Vertices: one per active edge; its id is the rank of the key a * 7 + d (a linear) among the active
+ * edges, ascending.  With b the upper node, t = (iso - v_a) / (v_b - v_a) and, per component c,
+ * pos_c = axis[a_c] + t * (axis[b_c] - axis[a_c]): fp32, every operation rounded on its own, a true
+ * division.  t is in [0, 1] for finite values; an infinite or NaN value gives what IEEE arithmetic
+ * gives (a NaN t makes all three components NaN; which NaN -- sign, payload -- is not specified).
+ * Tetrahedra: cell c = (ix (n - 1) + iy) (n - 1) + iz has six, tau = 0..5 the tau-th permutation
+ * (a, b, c) of the axes (x, y, z) in lexicographic order, with corners (in tetrahedron order)
+ * 0, bit(a), bit(a) | bit(b), 7, where bit(x) = 4, bit(y) = 2, bit(z) = 1.
+ * Triangles of a tetrahedron, as triples of its edges: none with 0 or 4 corners inside; with one
+ * corner L alone on its side (1 or 3 inside) and the others P < Q < R in tetrahedron order,
+ * (LP, LQ, LR); with A < B inside and C < D outside, (AC, AD, BD) then (AC, BD, BC).
+ * Orientation: with each vertex at its edge's midpoint in index space, the normal (v1 - v0) x
+ * (v2 - v0) must point from the centroid of the tetrahedron's inside corners to that of its outside
+ * corners; if not, the last two entries are swapped.  Then the face is rotated cyclically so that its
+ * smallest vertex id comes first.  Normals point out of the solid, towards the lower values.
+ * Faces: int32 triples of vertex ids in ascending (c, tau, triangle) order.  A face of zero area is
+ * possible (a node equal to iso gives t = 0 on its edges); the mesh stays combinatorially closed.
+ * No atomics, no workgroup waits on another: the result is a pure function of the inputs.  Both
+ * launching entries are stream-ordered and never synchronise; argument errors return CN_EINVAL
+ * before any launch.  Not provided: vertex normals, simplification, vertex colours. */
+
+/* Bytes of the workspace cn_isosurface_count fills and cn_isosurface_emit reads, or -1 for n outside
+ * 2..513.  Layout, each array padded to a multiple of 16 bytes, N = n^3 nodes and B = ceil(N / 256)
+ * workgroups: the nodes' words (uint32: bits 0..6 the mask of the active edges the node owns, bits
+ * 7..10 its cell's triangle count, bits 11..18 the cell's inside bits by corner), their exclusive
+ * vertex offsets (int32), their exclusive face offsets (int32), the workgroups' exclusive vertex
+ * offsets (int32, B), their exclusive face offsets (int32, B):
+ *   bytes = 3 * pad16(4 N) + 2 * pad16(4 B). */
+int64_t cn_isosurface_workspace_bytes(int64_t n);
+
+/* Classify every node, scan, and leave every node's vertex and face offsets in the workspace (three
+ * launches): counts[0] = V, the number of vertices, counts[1] = T, the number of faces (device
+ * int64).  workspace: cn_isosurface_workspace_bytes(n) bytes, 8-byte aligned.
+ * CN_EINVAL: nodes, workspace or counts NULL; n outside 2..513; iso NaN or infinite; workspace or
+ * counts not 8-byte aligned. */
+int cn_isosurface_count(const float* nodes, int64_t n, float iso, void* workspace, int64_t* counts,
+                        cn_stream_t stream);
+
+/* The mesh of the grid cn_isosurface_count classified (same nodes, n and iso; workspace as it left
+ * it, only read here): vertices (max_vertices, 3) fp32 and faces (max_faces, 3) int32.  A vertex or
+ * face whose rank is >= its capacity is not stored and nothing is written past the capacity's rows;
+ * a capacity of 0 skips that output, whose pointer may then be NULL.  One launch per output.
+ * CN_EINVAL: nodes, axis or workspace NULL; n outside 2..513; iso NaN or infinite; a negative
+ * capacity; a NULL output with a capacity above 0; workspace not 8-byte aligned. */
+int cn_isosurface_emit(const float* nodes, const float* axis, int64_t n, float iso, const void* workspace,
+                       int64_t max_vertices, int64_t max_faces, float* vertices, int32_t* faces,
+                       cn_stream_t stream);
+
 /* --- Backward (autograd through the eval / train step) ------------------
  * The gradients loss.backward() takes through the path in the reference's
  * test-time optimisation (view_synthesis/eval.py) and training step:
