@@ -17,6 +17,12 @@
  *   - Return value: 0 on success; a negative CN_E* for an argument error
  *     (nothing launched); a positive hipError_t from the launch.
  *   - Reentrant; one process per GPU (mirrors mp.spawn in train.py/eval.py).
+ *   - Buffer contract.  An output is WRITTEN (every documented element stored, whatever it held) or
+ *     ACCUMULATED (added to what the caller put there: zeros, or a running sum).  A `workspace` is
+ *     scratch: its contents on entry are ignored -- it may hold anything, NaNs included -- unless the
+ *     entry says which earlier call must have filled it.  No entry point stores outside the
+ *     documented extent of a buffer, and a strided output (ldc > row length) keeps its gap columns.
+ *     tests/buffers.py makes this executable (NaN-poisoned allocations, trailing guards).
  */
 #ifndef CODENERF_H_
 #define CODENERF_H_
@@ -342,9 +348,9 @@ int64_t cn_occupancy_cull_workspace_bytes(int64_t n_rays, int64_t n_samples);
  * points-mode input of cn_radiance_field, cn_radiance_field_fold and cn_density_field -- pts, rd =
  * vdir, n_rays = chunk_rows = M', n_samples = 1, code_index = code_out (or none with one code
  * row) -- which computes for each the bits the unculled field computes for sample k.
- * workspace: cn_occupancy_cull_workspace_bytes(n_rays, n_samples) bytes, 8-byte aligned, written
- * here and read by cn_occupancy_expand.  Three launches (masks, a scan of the rays' counts, emit):
- * no atomics, the result is deterministic.
+ * workspace: cn_occupancy_cull_workspace_bytes(n_rays, n_samples) bytes, 8-byte aligned; contents on
+ * entry are ignored; written here and read by cn_occupancy_expand.  Three launches (masks, a scan of
+ * the rays' counts, emit): no atomics, the result is deterministic.
  * CN_EINVAL: a required pointer NULL (code_index and code_out are optional); n_rays <= 0;
  * n_samples outside 1..512; n_rays * n_samples > INT32_MAX; chunk_rows <= 0; g as above; workspace
  * or count not 8-byte aligned. */
@@ -354,9 +360,9 @@ int cn_occupancy_cull(const float* ro, const float* rd, const float* z, int64_t 
                       float* pts, float* vdir, int64_t* code_out, cn_stream_t stream);
 
 /* The gather back: raw (n_rays, n_samples, 4) row k = raw_compact (M', 4) row j where
- * sample_index[j] = k, and [0, 0, 0, CN_EMPTY_SIGMA_RAW] for a culled k.  workspace: as
- * cn_occupancy_cull of the same sizes left it.  raw and raw_compact 16-byte aligned; raw_compact
- * may be NULL only when the caller knows M' = 0.
+ * sample_index[j] = k, and [0, 0, 0, CN_EMPTY_SIGMA_RAW] for a culled k.  workspace: what
+ * cn_occupancy_cull (or cn_weight_cull) of the same sizes left there, only read here.  raw and
+ * raw_compact 16-byte aligned; raw_compact may be NULL only when the caller knows M' = 0.
  * CN_EINVAL: workspace or raw NULL; a size cn_occupancy_cull refuses; raw or raw_compact
  * misaligned; workspace not 8-byte aligned. */
 int cn_occupancy_expand(const float* raw_compact, const void* workspace, int64_t n_rays, int64_t n_samples,
@@ -384,8 +390,9 @@ int cn_occupancy_expand(const float* raw_compact, const void* workspace, int64_t
 
 /* cn_occupancy_cull with the kept test above in place of the grid lookup: weights (n_rays,
  * n_samples) as cn_volume_render wrote them.  Every output, the workspace
- * (cn_occupancy_cull_workspace_bytes) and its layout are cn_occupancy_cull's -- the same scan and
- * emit launches follow the mask launch -- so cn_occupancy_expand reads the state it leaves.
+ * (cn_occupancy_cull_workspace_bytes; contents on entry are ignored) and its layout are
+ * cn_occupancy_cull's -- the same scan and emit launches follow the mask launch -- so
+ * cn_occupancy_expand reads the state it leaves.
  * Stream-ordered, no atomics, compact rows in ascending k.
  * CN_EINVAL before any launch: weights NULL; eps_weight or eps_tail negative or NaN; and every
  * size, pointer and alignment rule of cn_occupancy_cull. */
@@ -448,7 +455,8 @@ int64_t cn_isosurface_workspace_bytes(int64_t n);
 
 /* Classify every node, scan, and leave every node's vertex and face offsets in the workspace (three
  * launches): counts[0] = V, the number of vertices, counts[1] = T, the number of faces (device
- * int64).  workspace: cn_isosurface_workspace_bytes(n) bytes, 8-byte aligned.
+ * int64).  workspace: cn_isosurface_workspace_bytes(n) bytes, 8-byte aligned; contents on entry are
+ * ignored.
  * CN_EINVAL: nodes, workspace or counts NULL; n outside 2..513; iso NaN or infinite; workspace or
  * counts not 8-byte aligned. */
 int cn_isosurface_count(const float* nodes, int64_t n, float iso, void* workspace, int64_t* counts,
@@ -492,7 +500,8 @@ int cn_encode_inputs(const float* pts, const float* ro, const float* rd, const f
                      int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz, const float* freqs_dir,
                      float* x, cn_stream_t stream);
 
-/* Floats of scratch cn_field_backward needs for M sample rows. */
+/* Floats of scratch cn_field_backward needs for M sample rows (workspace: contents on entry are
+ * ignored). */
 int64_t cn_field_backward_workspace_floats(int64_t m);
 /* Offset (floats) of the (M, 90) dL/dx rows inside that scratch after cn_field_backward. */
 int64_t cn_field_backward_dx_offset(int64_t m);
@@ -520,7 +529,8 @@ int cn_field_backward(const float* const* params, const float* saved, const floa
 /* cn_field_backward with the GEMMs' arithmetic chosen by fmt: CN_FMT_F32 (exact-product
  * fp32 MFMA, what cn_field_backward runs) or CN_FMT_BF16X3 (every dX / dW GEMM as
  * Ah.Bh + Ah.Bl + Al.Bh on bf16 MFMA with fp32 accumulation, ~2^-17 relative error per
- * product; the training step).  Same arguments, outputs and workspace otherwise. */
+ * product; the training step).  Same arguments, outputs and workspace (contents on entry are ignored)
+ * otherwise. */
 int cn_field_backward_fmt(int fmt, const float* const* params, const float* saved, const float* x_enc,
                           const float* d_raw, const float* pts, const float* ro, const float* rd,
                           const float* z, int64_t n_rays, int64_t n_samples, int64_t chunk_rows,
@@ -533,7 +543,8 @@ int cn_field_backward_fmt(int fmt, const float* const* params, const float* save
  * (eval.py:141-160; the reference's weight gradients are never read there).
  * Forward: cn_radiance_field_masks = cn_radiance_field on a CN_FMT_BF16X3 pack
  * that also writes the ReLU masks of layer_xyz1 / layer_xyz2 / layer_dir1 /
- * layer_dir2 (cn_field_mask_words(M) uint32 words).  Backward: one launch from
+ * layer_dir2 (cn_field_mask_words(M) uint32 words; the bits of the last 128-sample tile's rows
+ * past M are whatever the kernel leaves and no backward reads them).  Backward: one launch from
  * d_raw (M, 4) through the whole field on a CN_FMT_BF16X3_T pack of the same
  * weights: g_code (n_codes, CN_CODE_BIAS_STRIDE) ACCUMULATED as in
  * cn_field_backward (feed cn_code_bias_backward for dz_s / dz_t), d_pts (M, 3)
@@ -571,9 +582,10 @@ int cn_field_backward_fused(int fmt_t, const float* packed_t, const uint32_t* ma
 /* The same backward without float atomics (eval.py:145-160's backward, bit-reproducible): with
  * n_codes == 1 and n_samples % 32 (bf16x3) / % 16 (fp32) == 0 the kernel writes per-workgroup g_code
  * rows and per-wave / per-sample ray-gradient terms into workspace
- * (cn_field_backward_fused_workspace_floats(fmt_t, n_rays, n_samples) floats, 16-B aligned), and two
- * short launches add them into g_code, d_ro and d_rd in a fixed order (g_code / d_ro / d_rd are still
- * ACCUMULATED).  Other shapes, or workspace NULL, run cn_field_backward_fused. */
+ * (cn_field_backward_fused_workspace_floats(fmt_t, n_rays, n_samples) floats, 16-B aligned; contents on
+ * entry are ignored: a wave or workgroup without rows stores its zero row or is skipped by the sums),
+ * and two short launches add them into g_code, d_ro and d_rd in a fixed order (g_code / d_ro / d_rd are
+ * still ACCUMULATED).  Other shapes, or workspace NULL, run cn_field_backward_fused. */
 int64_t cn_field_backward_fused_workspace_floats(int fmt_t, int64_t n_rays, int64_t n_samples);
 int cn_field_backward_fused_ws(int fmt_t, const float* packed_t, const uint32_t* masks, const float* d_raw,
                                const float* pts, const float* ro, const float* rd, const float* z, int64_t n_rays,
@@ -619,7 +631,8 @@ int cn_field_backward_fused_multi(int fmt_t, const cn_field_fused_bwd* fields, i
  * slot).  save holds cn_field_train_saved_floats(CN_FMT_F32_W16, M) floats.
  * Backward: the fused dX chain of cn_field_backward_fused on the CN_FMT_F32_W16_T pack (g_code,
  * d_pts / d_ro / d_rd as there; g_code required) that also writes every layer's masked input
- * gradient into workspace (cn_field_backward_train_workspace_floats(M) floats), then the weight
+ * gradient into workspace (cn_field_backward_train_workspace_floats(M) floats; contents on entry are
+ * ignored, the partial tiles of the dW plans included), then the weight
  * and bias gradients dW = dPre^T X as split-M fp32 MFMA GEMMs over those planes, saved and x_enc
  * (cn_encode_inputs; or x_enc NULL: the forward's own encodings from saved's encoding plane, fp32,
  * or generated inside the dW kernels, bf16x3), reduced
@@ -635,7 +648,8 @@ int cn_radiance_field_train_w16(const float* packed, const float* code_bias, con
  * 32x32x16; masks cn_field_mask_words_fmt(CN_FMT_BF16X3, M) words, the same fp32 planes), and
  * fmt_t the matching transposed pack (CN_FMT_F32_W16_T / CN_FMT_BF16X3_T; the bf16x3 dW GEMMs
  * are 3xbf16 too).  bf16x3: one code row per 32-sample wave (n_codes == 1 or n_samples % 32 == 0);
- * its save buffer holds 5 * M * 256 + 256 floats (the last row is scratch for padding lanes).
+ * its save buffer holds 5 * M * 256 + 256 floats (the last row is scratch for padding lanes: contents
+ * on entry are ignored, and what it holds afterwards is unspecified and never read).
  * cn_field_train_saved_floats: the save buffer's floats for fmt and M (-1: bad arguments). */
 int64_t cn_field_train_saved_floats(int fmt, int64_t m);
 int cn_radiance_field_train_fmt(int fmt, const float* packed, const float* code_bias, const int64_t* code_index,
@@ -662,11 +676,11 @@ int cn_field_backward_train_fmt(int fmt_t, const float* packed_t, const float* c
  * calls for predict_radiance_and_render's coarse and fine fields, nerf/__init__.py:81-89 under
  * train.py:112's loss.backward(): the fine depths are detached, point_sampler.py:115, so the two
  * backwards are independent).  Each field: the arguments of cn_field_backward_train_fmt, with its own
- * workspace.  With two fp32 fields on rays + depths that both take the batched dW plan and the forward's
- * encoding plane (every runnable training config): ONE dX launch, ONE batched dW launch (layer_xyz1's
- * dW among its jobs), ONE DIRS-pass launch and ONE reduction launch for both, each running every field's
- * workgroups as its own launch would -- the gradients are bitwise those of the per-field calls.  Otherwise the fields run one after
- * the other.  n_fields 1 or 2. */
+ * workspace (contents on entry are ignored).  With two fp32 fields on rays + depths that both take the
+ * batched dW plan and the forward's encoding plane (every runnable training config): ONE dX launch, ONE
+ * batched dW launch (layer_xyz1's dW among its jobs), ONE DIRS-pass launch and ONE reduction launch for
+ * both, each running every field's workgroups as its own launch would -- the gradients are bitwise
+ * those of the per-field calls.  Otherwise the fields run one after the other.  n_fields 1 or 2. */
 typedef struct cn_field_train_bwd {
   const float* packed_t;
   const float* const* params;
@@ -699,8 +713,8 @@ int cn_code_bias_backward(const float* const* params, const float* z_s, const fl
                           const float* g_code, float* dz_s, float* dz_t, float* const* grads,
                           cn_stream_t stream);
 /* The same backward in two launches with a caller-provided workspace
- * (cn_code_bias_backward_workspace_floats(n_codes) floats): each code's layers and
- * reductions are formed once, split over 64 workgroups, instead of once per workgroup.
+ * (cn_code_bias_backward_workspace_floats(n_codes) floats; contents on entry are ignored): each code's
+ * layers and reductions are formed once, split over 64 workgroups, instead of once per workgroup.
  * Bitwise the same results as cn_code_bias_backward.  accumulate_dz = 1: dz_s / dz_t +=
  * the code gradients instead of = (the training step points them at the code tables'
  * gradient rows, so the coarse and fine fields' code gradients add up in place --
@@ -708,8 +722,10 @@ int cn_code_bias_backward(const float* const* params, const float* z_s, const fl
 int64_t cn_code_bias_backward_workspace_floats(int64_t n_codes);
 /* The code backward on the forward's code-layer activations (code_act of cn_field_prepare_models),
  * first half: ds1 / ds2 / dt1 (ReLU-masked by code_act) into the workspace
- * (cn_code_bias_backward_workspace_floats) and the code layers' / code halves' parameter gradients
- * added into grads (optional) -- no code layer is recomputed.  cn_code_dz forms dz from it. */
+ * (cn_code_bias_backward_workspace_floats; contents on entry are ignored; rows 3..5 of each code that
+ * some sample used are written here, the rest stays as it was) and the code layers' / code halves'
+ * parameter gradients added into grads (optional) -- no code layer is recomputed.  cn_code_dz forms dz
+ * from it. */
 int cn_code_bias_backward_act(const float* const* params, const float* z_s, const float* z_t, int64_t n_codes,
                               const float* code_act, const float* g_code, float* const* grads, float* workspace,
                               cn_stream_t stream);
@@ -724,7 +740,8 @@ typedef struct cn_code_act_job {
 } cn_code_act_job;
 int cn_code_bias_backward_act_multi(const cn_code_act_job* jobs, int n_jobs, const float* z_s, const float* z_t,
                                     int64_t n_codes, cn_stream_t stream);
-/* One field's part of cn_code_dz: its parameters, g_code and cn_code_bias_backward_act's workspace. */
+/* One field's part of cn_code_dz: its parameters, g_code and the workspace as cn_code_bias_backward_act
+ * of the same field left it (only read: rows 3..5 of every code whose g_code row is not all zero). */
 typedef struct cn_code_dz_job {
   const float* const* params;
   const float* g_code;
@@ -776,7 +793,7 @@ int cn_ray_points_backward(const float* g_pts, const float* z, int64_t n_rays, i
  * eval; or whole tables with expand 1, train).  rgb_*: (n_rays, 3), either may be NULL;
  * target rows of target_stride floats (the first 3 are rgb).  n_code 0: no regulariser.
  * workspace: cn_render_loss_workspace_doubles(n_code) doubles (0: may be NULL) for the
- * multi-workgroup sums of large code tensors. */
+ * multi-workgroup sums of large code tensors; contents on entry are ignored. */
 int64_t cn_render_loss_workspace_doubles(int64_t n_code);
 int cn_render_loss(const float* rgb_coarse, const float* rgb_fine, const float* target,
                    int64_t target_stride, int64_t n_rays, const float* z_s, const float* z_t,
@@ -827,7 +844,8 @@ int cn_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* ex
 
 /* fp32 MFMA GEMMs the backward is built from (row-major, leading dims in floats):
  *   cn_gemm_nn: C[M][N] = A[M][K] B[K][N], zeroed where mask[m][n] <= 0 (mask may be NULL); K <= 288;
- *   cn_gemm_tn: C[N][K] += sum_m A[M][N] B[M][K] (accumulates). */
+ *   cn_gemm_tn: C[N][K] += sum_m A[M][N] B[M][K] (accumulates).
+ * With ldc above the row length (and ldm above N) the columns between the rows are left as they are. */
 int cn_gemm_nn(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
                const float* mask, int64_t ldm, int64_t M, int64_t N, int64_t K, cn_stream_t stream);
 int cn_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
@@ -839,9 +857,9 @@ int cn_gemm_nn_x3(const float* A, int64_t lda, const float* B, int64_t ldb, floa
 int cn_gemm_tn_x3(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
                   int64_t N, int64_t K, cn_stream_t stream);
 /* cn_gemm_tn (fmt CN_FMT_F32) or cn_gemm_tn_x3 (CN_FMT_BF16X3), deterministic: each workgroup
- * stores its partial N x K tile into workspace (cn_gemm_tn_workspace_floats(M, N, K) floats) and
- * a second pass adds the partials to C in a fixed order, so the result is bitwise reproducible
- * (the float-atomic flush of cn_gemm_tn is not). */
+ * stores its partial N x K tile into workspace (cn_gemm_tn_workspace_floats(M, N, K) floats; contents
+ * on entry are ignored) and a second pass adds the partials to C in a fixed order, so the result is
+ * bitwise reproducible (the float-atomic flush of cn_gemm_tn is not). */
 int64_t cn_gemm_tn_workspace_floats(int64_t M, int64_t N, int64_t K);
 int cn_gemm_tn_ws(int fmt, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
                   int64_t M, int64_t N, int64_t K, float* workspace, cn_stream_t stream);
