@@ -100,6 +100,10 @@ SIGNATURES = {
     "cn_fold_bias": (_i, [ctypes.POINTER(_p), _p, _i64, _p, _p]),
     "cn_mlp_forward_fold": (_i, [_p, _i, _p, _p, _p, _i64, _p, _i64, _p, _p]),
     "cn_radiance_field_fold": (_i, [_p, _i, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _fp, _fp, _p, _p]),
+    "cn_view_rows_bytes": (_i64, [_i64]),
+    "cn_view_rows": (_i, [_p, _i, _p, _p, _i64, _fp, _p, _p]),
+    "cn_radiance_field_fold_rows": (_i, [_p, _i, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _fp, _fp, _p,
+                                         _p]),
     "cn_field_prepare": (_i, [ctypes.POINTER(_p), _p, _p, _i64, _p, _p, _p, _p, _i64, _p]),
     "cn_field_prepare_models": (_i, [ctypes.POINTER(FieldPrep), _i, _p, _p, _i64, _p]),
     "cn_field_train_saved_floats": (_i64, [_i, _i64]),

@@ -431,15 +431,51 @@ def mlp_forward(packed: Tensor, cb: Tensor, x: Tensor, code_index: Optional[Tens
     return raw
 
 
+# The fewest samples per ray at which the folded kernel reads its view-direction term from a per-ray
+# table (cn_view_rows + cn_radiance_field_fold_rows) instead of computing it per sample.  A ray's row
+# costs one 1 KiB store and S 1 KiB loads against S x (7 of 223 k-steps of matrix work + the direction's
+# normalisation and encoding): at S = 1 (the culled renders' compact lists) the table is a pure loss.
+# Measured on MI355X at 2^21 samples per launch, table build included, table / in-kernel time
+# (profiles/viewrows/crossover.json): S = 1 1.082, 2 1.031, 4 1.000, 8 0.986, 16 0.977, 32 0.975, 64 0.975.
+VIEW_ROWS_MIN_SAMPLES = 8
+
+
+def view_rows(packed: Tensor, fold_bias: Tensor, rd: Tensor, freqs_dir: Sequence[float]) -> Tensor:
+    """cn_view_rows: per ray, fold_bias row 0 + W_dir1[:, 256:] enc(rd / |rd|) -> (R, 256), bit for bit
+    what the folded kernel's accumulators hold after its view-direction chunk.  ``packed``: the
+    "f32_w16_fold" pack."""
+    lib = _lib_ready()
+    packed, fold_bias, rd = _cuda(packed, "packed"), _cuda(fold_bias, "fold_bias"), _cuda(rd, "rd")
+    assert fold_bias.dim() == 2 and fold_bias.shape[1] == 256, "fold_bias must be (n_codes, 256)"
+    assert rd.dim() == 2 and rd.shape[1] == 3, "rd must be (num_rays, 3)"
+    assert len(freqs_dir) == 4, "the field kernel implements L_dir=4"
+    n = rd.shape[0]
+    nbytes = lib.cn_view_rows_bytes(n) if n else 0
+    assert nbytes >= 0, "cn_view_rows_bytes refused the ray count"
+    rows = torch.empty(nbytes // 4, device=rd.device, dtype=torch.float32).view(n, 256)
+    if n:
+        check(lib.cn_view_rows(ptr(packed), _fmt("f32_w16_fold"), ptr(fold_bias), ptr(rd), n,
+                               _lib.host_floats(freqs_dir), ptr(rows), stream_of(rd)), "cn_view_rows")
+    return rows
+
+
+_view_rows_table = view_rows   # radiance_field's keyword of the same name shadows the function there
+
+
 def radiance_field(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int, chunk_rows: int,
                    freqs_xyz: Sequence[float], freqs_dir: Sequence[float], pts: Optional[Tensor] = None,
                    ro: Optional[Tensor] = None, z: Optional[Tensor] = None,
                    code_index: Optional[Tensor] = None, precision: str = "f32",
-                   fold_bias: Optional[Tensor] = None) -> Tensor:
+                   fold_bias: Optional[Tensor] = None, view_rows: Optional[bool] = None) -> Tensor:
     """forward_pass (nerf/__init__.py:94-134) fused with the MLP -> raw (R, S, 4).
-    precision "f32_w16_fold": ``packed`` that format's pack and ``fold_bias`` = ops.fold_bias(params, cb)."""
+    precision "f32_w16_fold": ``packed`` that format's pack and ``fold_bias`` = ops.fold_bias(params, cb).
+    ``view_rows`` (that precision only): read layer_dir1's view-direction term from a per-ray table built
+    here (ops.view_rows) instead of computing it per sample -- the same bits.  None: where it pays, i.e.
+    geometry from rays, one code row, no code_index and n_samples >= VIEW_ROWS_MIN_SAMPLES; True forces it
+    (one code row without code_index required), False forces the in-kernel path."""
     lib = _lib_ready()
     fold = _fold_rows(precision, cb, fold_bias)
+    assert not view_rows or fold is not None, "view_rows goes with precision 'f32_w16_fold'"
     rd = _cuda(rd, "rd")
     n = rd.shape[0]
     if pts is not None:
@@ -455,7 +491,20 @@ def radiance_field(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int, chunk
         assert n_codes in (1, n), "codes must be one row or one row per ray"
     assert len(freqs_xyz) == 10 and len(freqs_dir) == 4, "the field kernel implements L_xyz=10, L_dir=4"
     raw = torch.empty(n, n_samples, 4, device=rd.device, dtype=torch.float32)
-    if n and fold is not None:
+    one_code = n_codes == 1 and code_index is None
+    if view_rows is None:
+        view_rows = fold is not None and pts is None and one_code and n_samples >= VIEW_ROWS_MIN_SAMPLES
+    elif view_rows:
+        if not one_code:
+            raise ValueError("view_rows=True needs one code row and no code_index: a table row holds code row 0's "
+                             "c_v1")
+    if n and fold is not None and view_rows:
+        rows = _view_rows_table(packed, fold, rd, freqs_dir)
+        check(lib.cn_radiance_field_fold_rows(ptr(packed), _fmt(precision), ptr(cb), ptr(fold), ptr(rows), None, 1,
+                                              ptr(pts), ptr(ro), ptr(rd), ptr(z), n, n_samples, chunk_rows,
+                                              _lib.host_floats(freqs_xyz), _lib.host_floats(freqs_dir), ptr(raw),
+                                              stream_of(rd)), "cn_radiance_field_fold_rows")
+    elif n and fold is not None:
         check(lib.cn_radiance_field_fold(ptr(packed), _fmt(precision), ptr(cb), ptr(fold), ptr(code_index), n_codes,
                                          ptr(pts), ptr(ro), ptr(rd), ptr(z), n, n_samples, chunk_rows,
                                          _lib.host_floats(freqs_xyz), _lib.host_floats(freqs_dir), ptr(raw),

@@ -553,6 +553,61 @@ extern "C" int cn_radiance_field_fold(const float* packed, int fmt, const float*
                             n_samples, chunk_rows, freqs_xyz, freqs_dir, raw, stream);
 }
 
+extern "C" int64_t cn_view_rows_bytes(int64_t n_rays) {
+  return (n_rays > 0 && n_rays <= INT64_MAX / (kHidden * 4)) ? n_rays * kHidden * 4 : -1;
+}
+
+extern "C" int cn_view_rows(const float* packed, int fmt, const float* fold_bias, const float* rd, int64_t n_rays,
+                            const float* freqs_dir, float* view_rows, cn_stream_t stream) {
+  const int rc = forward_fmt_status(fmt, true);
+  if (rc != CN_OK) return rc;
+  CN_CHECK_ARG(packed && fold_bias && rd && freqs_dir && view_rows);
+  CN_CHECK_ARG(n_rays > 0 && cn_view_rows_bytes(n_rays) > 0);
+  CN_CHECK_ARG(cn::aligned16(packed) && cn::aligned16(fold_bias) && cn::aligned16(view_rows));  // 16-B vector accesses
+  FieldArgs a = {};
+  a.packed = packed;
+  a.fold_bias = fold_bias;
+  a.rd = rd;
+  a.n_rays = n_rays;
+  for (int i = 0; i < 4; ++i) a.fd[i] = freqs_dir[i];
+  return launch_view_rows_w16(a, view_rows, cn::as_stream(stream));
+}
+
+extern "C" int cn_radiance_field_fold_rows(const float* packed, int fmt, const float* code_bias,
+                                           const float* fold_bias, const float* view_rows,
+                                           const int64_t* code_index, int64_t n_codes, const float* pts,
+                                           const float* ro, const float* rd, const float* z, int64_t n_rays,
+                                           int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz,
+                                           const float* freqs_dir, float* raw, cn_stream_t stream) {
+  const int rc = forward_fmt_status(fmt, true);
+  if (rc != CN_OK) return rc;
+  CN_CHECK_ARG(packed && code_bias && fold_bias && view_rows && rd && raw && freqs_xyz && freqs_dir);
+  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && chunk_rows > 0);
+  CN_CHECK_ARG(n_codes == 1 && !code_index);  // the rows hold code row 0's c_v1
+  CN_CHECK_ARG(pts || (ro && z));
+  CN_CHECK_ARG(n_rays <= INT64_MAX / n_samples && cn::ceil_div(n_rays * n_samples, kTile) <= 0x7fffffff);
+  CN_CHECK_ARG(cn_view_rows_bytes(n_rays) > 0);
+  CN_CHECK_ARG(cn::aligned16(raw) && cn::aligned16(fold_bias) && cn::aligned16(view_rows));
+  FieldArgs a = {};
+  a.packed = packed;
+  a.code_bias = code_bias;
+  a.fold_bias = fold_bias;
+  a.view_rows = view_rows;
+  a.n_codes = 1;
+  a.pts = pts;
+  a.ro = ro;
+  a.rd = rd;
+  a.z = z;
+  a.n_rays = n_rays;
+  a.n_samples = n_samples;
+  a.chunk_rows = chunk_rows;
+  a.m = n_rays * n_samples;
+  for (int i = 0; i < 10; ++i) a.fx[i] = freqs_xyz[i];
+  for (int i = 0; i < 4; ++i) a.fd[i] = freqs_dir[i];
+  a.raw = raw;
+  return launch_field_w16_fold_rows(pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream));
+}
+
 extern "C" int cn_density_field(const float* packed, int fmt, const float* code_bias, const int64_t* code_index,
                                 int64_t n_codes, const float* pts, const float* ro, const float* rd, const float* z,
                                 const float* x, int64_t x_stride, int64_t n_rays, int64_t n_samples,

@@ -55,6 +55,8 @@ struct FieldArgs {
   int64_t n_blocks;      // set by the backward launchers: the grid they launched
   // folded fp32 inference forward (CN_FMT_F32_W16_FOLD): (n_codes, 256) c_v1 rows of cn_fold_bias
   const float* fold_bias;
+  // its table variant (cn_radiance_field_fold_rows): (n_rays, 256) rows of cn_view_rows
+  const float* view_rows;
 };
 
 // The density-only forward (cn_density_field): the field's inputs (f.raw optional here; f.x rows
@@ -313,6 +315,11 @@ int64_t packed_floats_w16_fold();
 int launch_pack_w16_fold(const Params& P, float* packed, hipStream_t st);
 int launch_fold_bias(const Params& P, const float* code_bias, int64_t n_codes, float* fold_bias, hipStream_t st);
 int launch_field_w16_fold(int mode, FieldArgs& a, hipStream_t st);
+// the per-ray rows { c_v1 of code row 0 + the view-direction chunk's product } (a.packed the folded pack,
+// a.fold_bias, a.rd, a.n_rays, a.fd) and the folded forward that starts from them (a.view_rows; one code
+// row, geometry from points or rays)
+int launch_view_rows_w16(FieldArgs& a, float* rows, hipStream_t st);
+int launch_field_w16_fold_rows(int mode, FieldArgs& a, hipStream_t st);
 int launch_pack_w16t(const Params& P, float* packed, hipStream_t st);
 // code_bias + the CN_FMT_F32_W16 / _T packs + a zeroed buffer (any of them null: skipped), for one or
 // two models on the same codes, in one launch

@@ -169,10 +169,13 @@ __global__ void pack_w16_kernel(Params P, float* __restrict__ packed) {
 //   W_f = W_dir1[:, :256] W_out[1:, :256]                     (here, once per weight version)
 //   c_v1[code] = W_dir1[:, :256] c_feat[code] + b_dir1        (fold_bias_kernel, per code row)
 // The stream is the CN_FMT_F32_W16 one with fc_out's and layer_dir1's 16 chunks replaced by W_f's 8
-// (same fragment layout and column maps): xyz1 2 | xyz2 8 | fold 8 | view-dir 1 | dir2 8 | rgb 1.
+// (same fragment layout and column maps): xyz1 2 | xyz2 8 | view-dir 1 | fold 8 | dir2 8 | rgb 1.
+// The view-direction chunk comes before W_f's: what the accumulators hold after it -- c_v1 plus the
+// view-direction term -- depends on the ray alone, so a launch may read it from a per-ray table
+// (view_rows_kernel) and skip the chunk (kStreamRows).
 // The constants keep their places (the LDS copy is the unfolded kernel's); b_dir1's slot is zero,
 // b_dir1 lives in c_v1.
-constexpr int kFFold = kCL3, kFDir = 18, kFoldChunks = 28;  // dir2 from 19, rgb 27
+constexpr int kFDir = kCL3, kFFold = kFDir + 1, kFDir2 = kFFold + 8, kFoldChunks = 28;  // dir2 from 19, rgb 27
 constexpr int kFoldStreamFloats = kFoldChunks * kChunkQuads * 4;
 constexpr int kFoldPackedFloats = kFoldStreamFloats + kConsts;
 static_assert(kFoldChunks % kRing == 0, "cyclic stream: chunk c + 28 reuses chunk c's ring slot");
@@ -186,7 +189,7 @@ __global__ void pack_w16_fold_kernel(Params P, float* __restrict__ packed) {
       v = (j >= kCBD1 && j < kCBD2) ? 0.0f : pack_w16_const(P, j);
     } else {
       const int c = idx / (kChunkQuads * 4), rem = idx % (kChunkQuads * 4);
-      if (c >= kFFold && c < kFDir) {
+      if (c >= kFFold && c < kFDir2) {
         // W_f[row][col]: a 256-term dot product in double (each product exact), rounded once
         const int s = rem / (kStepQuads * 4), q = (rem % (kStepQuads * 4)) / 256;
         const int lane = (rem % 256) / 4, ob = 4 * q + rem % 4;
@@ -198,7 +201,7 @@ __global__ void pack_w16_fold_kernel(Params P, float* __restrict__ packed) {
         v = static_cast<float>(acc);
       } else {
         // the unfolded stream's chunk with the same contents
-        v = pack_w16_stream_elem(P, c < kFFold ? c : c + (kCDir - kFDir), rem);
+        v = pack_w16_stream_elem(P, c < kFDir ? c : (c == kFDir ? kCDir : c + (kCL5 - kFDir2)), rem);
       }
     }
     packed[idx] = v;
@@ -237,6 +240,7 @@ struct State {
   floatx4 acc[16];   // layer output accumulators
   floatx4 pre[4];    // the next chunk's first A fragments (read during this chunk's last k-step)
   floatx4 acc2[4];   // backward: the narrow chunks' accumulators (2 blocks x 2 chains)
+  floatx4 row[12];   // folded table variant: the view-direction row's first blocks on their way to the accumulators
   float denc[8];     // view-direction encoding, k-steps of the view-dir chunk
   float sig;         // sigma partial (this lane group's 64 features)
   int lane, g, wave;
@@ -313,7 +317,17 @@ __device__ __forceinline__ int stream_src_sigma(const State& s, int cn) {
 }
 // Which stream a chunk counter walks (dma_piece): a bool NOGEO converts to the first two.
 // kStreamFold: the folded pack's kFoldChunks chunks from cn = 0 in every tile, as kStreamFull.
-constexpr int kStreamFull = 0, kStreamNG = 1, kStreamSigma = 2, kStreamFold = 3;
+constexpr int kStreamFull = 0, kStreamNG = 1, kStreamSigma = 2, kStreamFold = 3, kStreamRows = 4;
+// kStreamRows: the folded pack without its view-direction chunk kFDir (the accumulators start from
+// the per-ray table instead); 27 is not a multiple of the ring, so the counter runs on across tiles
+// as the two above (folded mod lcm(27, ring) = 108 between tiles).
+constexpr int kRowsChunks = kFoldChunks - 1;
+static_assert((4 * kRowsChunks) % kRing == 0, "the table variant's counter folds mod 4 tiles");
+__device__ __forceinline__ int stream_src_rows(const State& s, int cn) {
+  int k = cn - s.cbase;
+  if (k >= kRowsChunks) k -= kRowsChunks;
+  return k + (k >= kFDir ? 1 : 0);
+}
 
 // One LDS-DMA piece: 1 KiB of chunk cn (piece p of 4 for this wave).
 template <int NG = kStreamFull>
@@ -321,6 +335,7 @@ __device__ __forceinline__ void dma_piece(const State& s, float4* lds, int cn, i
   const int src = NG == kStreamSigma ? stream_src_sigma(s, cn)
                   : NG == kStreamNG  ? stream_src_ng(s, cn)
                   : NG == kStreamFold ? (cn < kFoldChunks ? cn : cn - kFoldChunks)
+                  : NG == kStreamRows ? stream_src_rows(s, cn)
                                      : (cn < kChunks ? cn : cn - kChunks);
   const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(src * kChunkQuads + p * 64 * kWaves) * 16u);
   __builtin_amdgcn_raw_ptr_buffer_load_lds(
@@ -517,6 +532,19 @@ struct LazyXyz {
   }
 };
 
+// The lazy encodings of layer_xyz1's first chunk without the view-direction work of LazyXyz's second
+// (the density kernel and the folded kernel's table variant).
+struct LazyXyzOnly {
+  const LazyXyz l;
+  static constexpr bool kLazy = true;
+  template <int T>
+  __device__ __forceinline__ float at() const { return l.template at<T>(); }
+  template <int T>
+  __device__ __forceinline__ void prep() const {
+    if constexpr (T + 1 < 8) l.template pair<T + 1>();
+  }
+};
+
 // A 256-input layer: 8 chunks, B from s.act.
 template <int NG = kStreamFull, typename Post = NoPost>
 __device__ __forceinline__ void layer256(State& s, float4* lds, int& c, Post post = Post{}) {
@@ -662,6 +690,32 @@ struct XencStore {
   }
 };
 
+// The table variant's early row loads (chunk16's `post` of layer_xyz2): the first kRowEarly of the 16
+// ordinary 16-B loads per lane, into s.row (as many as the 256 registers of two waves per SIMD hold
+// beside layer_xyz2's operands without a spill; the rest follow once relu(h2) has left the
+// accumulators), issued in the layer's seventh chunk after its DMA (as LayerStores' stores: the next
+// barrier's counted vmcnt then waits for them too, which only asks more than it needs), so they fly
+// under a chunk and a half of MFMAs -- all 8 waves of a tile meet every chunk barrier together, and a
+// load waited for between two chunks stalls both waves of every SIMD at once.
+constexpr int kRowEarly = 12;
+struct RowLoads {
+  State& s;
+  const float* row;  // this lane's table row
+  bool on;           // the layer is layer_xyz2
+  template <int CI, int T>
+  __device__ __forceinline__ void step() const {
+    if constexpr (CI == 6 && T == 4) {
+      if (on) {
+        const floatx4* p = reinterpret_cast<const floatx4*>(row) + fresh(s.g);
+#pragma unroll
+        for (int ob = 0; ob < kRowEarly; ++ob) s.row[ob] = p[4 * ob];
+      }
+    }
+  }
+  template <int CI>
+  __device__ __forceinline__ void before_dma() const {}
+};
+
 // sigma = fc_out row 0 . [h2, zs2] + b: the h2 part (s.act = h2, this lane group's 64 features), the
 // code part from cn_code_bias (two packed chains: 32 v_pk_fma_f32 instead of one 64-deep fmaf chain)
 __device__ __forceinline__ float sigma_partial(const State& s, const float* clds) {
@@ -691,21 +745,85 @@ __device__ __forceinline__ float sigma_partial(const State& s, const float* clds
 // (5, m, 256) planes, feature 16 ob + 4 g + r: one 16-B store per block per lane).
 
 
+// decode_sample for the table variant: the point and the Q1 direction ray `dray` (decode_sample's
+// formulas) without the direction itself.
+template <int MODE>
+__device__ __forceinline__ SampleIn decode_sample_rows(const FieldArgs& a, int64_t rc, int64_t& dray) {
+  if constexpr (MODE == kFromEncoded) {
+    return decode_sample<MODE>(a, rc);
+  } else {
+    SampleIn in;
+    const int64_t S = a.n_samples;
+    const int64_t ray = rc / S, smp = rc - ray * S;
+    if constexpr (MODE == kFromPts) {
+      in.x[0] = a.pts[3 * rc]; in.x[1] = a.pts[3 * rc + 1]; in.x[2] = a.pts[3 * rc + 2];
+    } else {
+      const float zv = a.z[rc];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) in.x[j] = mul_add_rn(a.rd[3 * ray + j], zv, a.ro[3 * ray + j]);
+    }
+    const int64_t base = (ray / a.chunk_rows) * a.chunk_rows;
+    const int64_t rcnt = min(a.chunk_rows, a.n_rays - base);
+    dray = base + ((ray - base) * S + smp) % rcnt;
+    in.vd[0] = in.vd[1] = in.vd[2] = 0.0f;
+    in.nrm = 0.0f;
+    in.code_of = ray;
+    return in;
+  }
+}
+
+// The view-direction encoding's evaluator for one lane: fast_sincosf when this direction's largest
+// argument is in its range, ocml's sincosf otherwise.  It depends on the direction and the largest
+// |frequency| alone, so a finite direction's encoding -- and its row of the table -- has the same
+// bits whichever samples share its wave (folded kernel and view_rows_kernel).
+__device__ __forceinline__ bool view_dir_fast(const float (&vd)[3], float max_fd) {
+  const float da = fmaxf(fmaxf(fabsf(vd[0]), fabsf(vd[1])), fabsf(vd[2])) * max_fd;
+  return da <= kFastSinBound;  // false for NaN
+}
+// This lane group's 7 k-step values of the view-direction chunk (col_enc_dir; denc[7] = 0), all
+// evaluated up front: fd = the 4 frequencies (picked by selects: p / 3 varies with the lane).
+__device__ __forceinline__ void view_dir_enc(const float (&vd)[3], const float (&fd)[4], int g, bool fast,
+                                             float (&denc)[8]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int p = 4 * i + g, k = p / 3;
+    const float f = k == 0 ? fd[0] : (k == 1 ? fd[1] : (k == 2 ? fd[2] : fd[3]));
+    const float arg = __fmul_rn(pick3(vd, p % 3), f);
+    if (fast) fast_sincosf(arg, denc[i], denc[3 + i]);
+    else sincosf(arg, &denc[i], &denc[3 + i]);
+  }
+  denc[6] = g == 0 ? vd[0] : (g == 1 ? vd[1] : (g == 2 ? vd[2] : 0.0f));
+  denc[7] = 0.0f;
+}
+
 // FOLD (inference only: no masks, no planes): the CN_FMT_F32_W16_FOLD stream.  After relu(h2) and
 // sigma_partial -- chunks 0..9 and that epilogue are the unfolded kernel's, so sigma has its bits --
 // the accumulators start from the code's c_v1 row and take W_f's 8 chunks over relu(h2) and the
 // view-direction chunk: layer_dir1's pre-activation without fc_out's 8 chunks before it.
-template <int MODE, bool MASKS, bool SAVE = false, bool FOLD = false>
+//
+// ROWS (a FOLD variant; one code row, geometry from points or rays): the accumulators' start -- c_v1
+// plus the view-direction chunk's product, a function of the Q1 direction ray alone -- comes from the
+// per-ray table a.view_rows (view_rows_kernel, the same MFMAs over the same operands: the same bits).
+// The tile then decodes no direction, evaluates no view-direction encoding and streams the pack
+// without chunk kFDir (kStreamRows: 27 chunks, the counter c runs on across tiles from s.cbase).
+// Most of the 16 row loads are issued inside layer_xyz2 (RowLoads) into registers of their own and
+// move to the accumulators once relu(h2) has left them; the rest are issued then, ahead of
+// sigma_partial, and waited for with vmcnt(0) after it (the ring's pieces in flight before them retire
+// first, so the next barrier's counted vmcnt still holds).
+template <int MODE, bool MASKS, bool SAVE = false, bool FOLD = false, bool ROWS = false>
 __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4* lds, float* clds, float* crow_lds,
                                           int64_t tile, int& c) {
   static_assert(!FOLD || (!MASKS && !SAVE), "the folded kernel has no feat plane and no fc_out input gradient");
-  constexpr int NG = FOLD ? kStreamFold : kStreamFull;
+  static_assert(!ROWS || (FOLD && MODE != kFromEncoded), "the table variant is a folded kernel on geometry");
+  constexpr int NG = ROWS ? kStreamRows : (FOLD ? kStreamFold : kStreamFull);
   const int64_t row = tile * kTile + s.wave * 16 + (s.lane & 15);
   const bool valid = row < a.m;
   const int64_t rc = valid ? row : a.m - 1;
+  if constexpr (ROWS) s.cbase = c;
 
   // ---- per-sample inputs, code row (ordinary loads: the in-flight DMA retires with them)
-  const SampleIn in = decode_sample<MODE>(a, rc);
+  int64_t dray = 0;  // ROWS: the Q1 direction ray, the table row
+  const SampleIn in = ROWS ? decode_sample_rows<MODE>(a, rc, dray) : decode_sample<MODE>(a, rc);
   s.crow = static_cast<int>(code_row(a, in.code_of));
   const int crow0 = __builtin_amdgcn_readfirstlane(s.crow);
   s.uniform_code = __builtin_amdgcn_readfirstlane(__ballot(s.crow != crow0) == 0 ? 1 : 0) != 0;
@@ -743,12 +861,18 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
   // ---- encodings (lane group g owns pairs p = 4 i + g) and layer_xyz1 (63 -> 256): 2 chunks of
   // encoding k-steps.  Lazily (LazyXyz) when every lane's arguments are in fast_sincosf's range,
   // else all evaluated up front with sincosf.
-  bool lazy = false;
+  // FOLD: the two encodings' evaluators are chosen independently, so that the table variant, which
+  // sees no direction, returns the in-kernel path's bits.  The points' evaluator depends on the wave's
+  // points alone (`xs_fast`), the view direction's on its lane's direction alone (view_dir_fast); the
+  // up-front path below, which a wave also takes for another lane's direction, honours both.
+  bool lazy = false, dir_fast = true, xs_fast = false;
   if constexpr (MODE != kFromEncoded) {
     const float xa = fmaxf(fmaxf(fabsf(in.x[0]), fabsf(in.x[1])), fabsf(in.x[2])) * clds[kCFreq + 14];
-    const float da = fmaxf(fmaxf(fabsf(in.vd[0]), fabsf(in.vd[1])), fabsf(in.vd[2])) * clds[kCFreq + 15];
-    const bool ok = xa <= kFastSinBound && da <= kFastSinBound;  // false for NaN
+    dir_fast = ROWS || view_dir_fast(in.vd, clds[kCFreq + 15]);
+    const bool ok = xa <= kFastSinBound && dir_fast;  // false for NaN
     lazy = __builtin_amdgcn_readfirstlane(__ballot(!ok) == 0 ? 1 : 0) != 0;
+    if constexpr (FOLD && !ROWS)
+      xs_fast = __builtin_amdgcn_readfirstlane(__ballot(!(xa <= kFastSinBound)) == 0 ? 1 : 0) != 0;
   }
   if (lazy) {
     if constexpr (MODE != kFromEncoded) {
@@ -766,11 +890,17 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
       const LazyXyz l0{enc, s.denc, in.x, in.vd, fr, g, false};
       l0.pair<0>();
       bias_from(s, clds + kCB1);
-      chunk16<8, 0, NG>(s, lds, c + 0, l0);
-      if constexpr (SAVE)
-        chunk16<8, 0, NG>(s, lds, c + 1, LazyXyz{enc, s.denc, in.x, in.vd, fr, g, true}, XencStore{s, a, tile, enc});
-      else
-        chunk16<8, 0, NG>(s, lds, c + 1, LazyXyz{enc, s.denc, in.x, in.vd, fr, g, true});
+      if constexpr (ROWS) {
+        // no view-direction pairs to evaluate in the second chunk: the plain k-step pattern there
+        chunk16<8, 0, NG>(s, lds, c + 0, LazyXyzOnly{l0});
+        chunk16<8, 0, NG>(s, lds, c + 1, ArrB<8>{enc});
+      } else {
+        chunk16<8, 0, NG>(s, lds, c + 0, l0);
+        if constexpr (SAVE)
+          chunk16<8, 0, NG>(s, lds, c + 1, LazyXyz{enc, s.denc, in.x, in.vd, fr, g, true}, XencStore{s, a, tile, enc});
+        else
+          chunk16<8, 0, NG>(s, lds, c + 1, LazyXyz{enc, s.denc, in.x, in.vd, fr, g, true});
+      }
     }
   } else {
     if constexpr (MODE != kFromEncoded) {
@@ -781,7 +911,8 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
         const int pc = p < 30 ? p : 0;
         const float arg = __fmul_rn(pick3(in.x, pc % 3), clds[kCFreq + pc / 3]);
         float sn, cs;
-        sincosf(arg, &sn, &cs);
+        if (FOLD && xs_fast) fast_sincosf(arg, sn, cs);  // here for a direction's sake: the lazy path's bits
+        else sincosf(arg, &sn, &cs);
         if (i == 7 && p >= 30) {  // groups 2, 3: raw inputs
           sn = s.g == 2 ? in.x[0] : in.x[2];
           cs = s.g == 2 ? in.x[1] : 0.0f;
@@ -789,13 +920,20 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
         enc[i] = sn;
         enc[8 + i] = cs;
       }
+      if constexpr (FOLD) {
+        if constexpr (!ROWS) {
+          const float fd[4] = {clds[kCFreq + 10], clds[kCFreq + 11], clds[kCFreq + 12], clds[kCFreq + 13]};
+          view_dir_enc(in.vd, fd, g, dir_fast, s.denc);
+        }
+      } else {
 #pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const int p = 4 * i + g;
-        const float arg = __fmul_rn(pick3(in.vd, p % 3), clds[kCFreq + 10 + p / 3]);
-        sincosf(arg, &s.denc[i], &s.denc[3 + i]);
+        for (int i = 0; i < 3; ++i) {
+          const int p = 4 * i + g;
+          const float arg = __fmul_rn(pick3(in.vd, p % 3), clds[kCFreq + 10 + p / 3]);
+          sincosf(arg, &s.denc[i], &s.denc[3 + i]);
+        }
+        s.denc[6] = s.g == 0 ? in.vd[0] : (s.g == 1 ? in.vd[1] : (s.g == 2 ? in.vd[2] : 0.0f));
       }
-      s.denc[6] = s.g == 0 ? in.vd[0] : (s.g == 1 ? in.vd[1] : (s.g == 2 ? in.vd[2] : 0.0f));
     }
     s.denc[7] = 0.0f;
     bias_from(s, clds + kCB1);
@@ -808,8 +946,8 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
   c += 2;
 
   // ---- layer_xyz2, fc_out, layer_dir1 (+ view-dir chunk), layer_dir2
-  // (FOLD: the kOut turn runs the folded layer -- c_v1, W_f's chunks, the view-dir chunk -- and
-  // there is no kDir1 turn)
+  // (FOLD: the kOut turn runs the folded layer -- c_v1, the view-dir chunk, W_f's chunks; ROWS: the
+  // table row in place of the first two -- and there is no kDir1 turn)
   for (int layer = kXyz2; layer <= kDir2; ++layer) {
     if (FOLD && layer == kDir1) continue;
     // activation of the previous layer's outputs: ReLU, none after fc_out (feat); its mask words
@@ -823,16 +961,34 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
     }
     const LayerStores<MASKS, SAVE> st{s, a, tile, layer == kXyz2 ? 0 : (layer == kOut ? 1 : (layer == kDir2 ? 2 : -1)),
                                      layer - kXyz2, mw};
+    if (ROWS && layer == kOut) {
+      // the accumulators are free (relu(h2) sits in s.act): the row's last blocks fly over sigma_partial
+      const floatx4* p = reinterpret_cast<const floatx4*>(a.view_rows + dray * kHidden) + fresh(s.g);
+#pragma unroll
+      for (int ob = kRowEarly; ob < 16; ++ob) s.acc[ob] = p[4 * ob];
+      __builtin_amdgcn_sched_barrier(0);
+    }
     if (layer == kOut) {
       s.sig = sigma_partial(s, clds);
     }
     if (layer == kXyz2) bias_code(s, a, crow_lds, kCbXyz2);
+    else if (ROWS && layer == kOut) {
+      // the table row's first blocks, loaded during layer_xyz2 (RowLoads)
+#pragma unroll
+      for (int ob = 0; ob < kRowEarly; ++ob) s.acc[ob] = s.row[ob];
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the last blocks, and the ring's pieces before them
+    }
     else if (FOLD && layer == kOut) bias_fold(s, a, crow_lds);
     else if (layer == kOut) bias_code(s, a, crow_lds, kCbFeat);
     else bias_from(s, clds + (layer == kDir1 ? kCBD1 : kCBD2));
     __builtin_amdgcn_sched_barrier(0);
-    layer256<NG>(s, lds, c, st);
-    if (layer == (FOLD ? kOut : kDir1)) {
+    if (FOLD && !ROWS && layer == kOut) {
+      chunk16<7, 0, NG>(s, lds, c, ArrB<0>{s.denc});
+      c += 1;
+    }
+    if constexpr (ROWS) layer256<NG>(s, lds, c, RowLoads{s, a.view_rows + dray * kHidden, layer == kXyz2});
+    else layer256<NG>(s, lds, c, st);
+    if (!FOLD && layer == kDir1) {
       chunk16<7, 0, NG>(s, lds, c, ArrB<0>{s.denc});
       c += 1;
     }
@@ -917,7 +1073,7 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
 }
 
 
-template <int MODE, bool MASKS, bool SAVE = false, bool FOLD = false>
+template <int MODE, bool MASKS, bool SAVE = false, bool FOLD = false, bool ROWS = false>
 __global__ __launch_bounds__(kThreads, 2) void field_w16_kernel(FieldArgs a) {
   // ONE LDS object (a second one makes hipcc wait vmcnt(0) before ring reads): the DMA
   // ring, then the constants, then one code-bias row per wave
@@ -927,7 +1083,8 @@ __global__ __launch_bounds__(kThreads, 2) void field_w16_kernel(FieldArgs a) {
   s.lane = threadIdx.x & 63;
   s.g = s.lane >> 4;
   s.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  constexpr int NG = FOLD ? kStreamFold : kStreamFull;
+  constexpr int NG = ROWS ? kStreamRows : (FOLD ? kStreamFold : kStreamFull);
+  s.cbase = 0;
   s.wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.packed), 0,
                                              (FOLD ? kFoldPackedFloats : kPackedFloats) * 4, 0x00020000);
   s.voff = static_cast<unsigned>(s.wave * 64 + s.lane) * 16u;
@@ -947,12 +1104,62 @@ __global__ __launch_bounds__(kThreads, 2) void field_w16_kernel(FieldArgs a) {
   const int64_t n_tiles = (a.m + kTile - 1) / kTile;
   int c = 0;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    c = 0;
-    field_tile<MODE, MASKS, SAVE, FOLD>(s, a, lds, clds, crow_lds, tile, c);
+    if constexpr (ROWS) {
+      // 27 chunks per tile: the counter runs on (ring slot c & 3), folded mod lcm(27, ring)
+      if (c >= 4 * kRowsChunks) c -= 4 * kRowsChunks;
+    } else {
+      c = 0;
+    }
+    field_tile<MODE, MASKS, SAVE, FOLD, ROWS>(s, a, lds, clds, crow_lds, tile, c);
   }
   // the last tile prefetched chunks 0..2 of a tile that does not exist: they must land
   // before the workgroup's LDS is released
   __builtin_amdgcn_s_waitcnt(0x0F70);
+}
+
+
+// ================================================================ per-ray view-direction rows
+// rows[ray] (256 floats, feature order) = what the folded kernel's accumulators hold after
+// { c_v1 of code row 0; the view-direction chunk over enc(view_dir(ray)) }: the same view_dir, the
+// same evaluator choice (view_dir_fast), the same v_mfma_f32_16x16x4_f32 chain per block over the
+// same A fragments (chunk kFDir of the pack, read from global memory: 28 KiB, cache resident) in the
+// same k-step order -- bit for bit the in-kernel path's values.  16 rays per wave: lane l holds ray
+// l & 15 and lane group g = l >> 4 its k-step inputs, as a field tile's wave.  Rays past n_rays
+// repeat the last one and store nothing.
+constexpr int kVrThreads = 256, kVrRays = 16 * (kVrThreads / 64);
+__global__ __launch_bounds__(kVrThreads) void view_rows_kernel(FieldArgs a, float* __restrict__ rows) {
+  const int lane = threadIdx.x & 63, g = lane >> 4;
+  const int64_t ray = (int64_t)blockIdx.x * kVrRays + (threadIdx.x >> 6) * 16 + (lane & 15);
+  const bool valid = ray < a.n_rays;
+  float vd[3];
+  view_dir(a, valid ? ray : a.n_rays - 1, vd);
+  const float fd[4] = {a.fd[0], a.fd[1], a.fd[2], a.fd[3]};
+  float md = 0.0f;  // load_consts' largest |fd|
+#pragma unroll
+  for (int k = 0; k < 4; ++k) md = fmaxf(md, fabsf(fd[k]));
+  float denc[8];
+  view_dir_enc(vd, fd, g, view_dir_fast(vd, md), denc);
+  floatx4 acc[16];
+  const floatx4* cv = reinterpret_cast<const floatx4*>(a.fold_bias) + g;
+#pragma unroll
+  for (int ob = 0; ob < 16; ++ob) acc[ob] = cv[4 * ob];
+  const floatx4* wa = reinterpret_cast<const floatx4*>(a.packed) + kFDir * kChunkQuads + lane;
+#pragma unroll
+  for (int t = 0; t < 7; ++t) {
+    floatx4 af[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) af[q] = wa[t * kStepQuads + q * 64];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[4 * q + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[q][j], denc[t], acc[4 * q + j], 0, 0, 0);
+  }
+  if (valid) {
+    floatx4* o = reinterpret_cast<floatx4*>(rows + ray * kHidden) + g;
+#pragma unroll
+    for (int ob = 0; ob < 16; ++ob) o[4 * ob] = acc[ob];
+  }
 }
 
 
@@ -973,18 +1180,6 @@ __global__ __launch_bounds__(kThreads, 2) void field_w16_kernel(FieldArgs a) {
 constexpr int kSigLdsQuads = kRing * kChunkQuads + (kLdsConsts + kWaves * 256) / 4;
 static_assert(kSigLdsQuads * 16 <= 160 * 1024, "LDS budget (density)");
 static_assert((2 * kSigmaChunks) % kRing == 0, "the density counter folds mod 2 tiles");
-
-// The lazy encodings of layer_xyz1's first chunk without the view-direction work of LazyXyz's second.
-struct LazyXyzOnly {
-  const LazyXyz l;
-  static constexpr bool kLazy = true;
-  template <int T>
-  __device__ __forceinline__ float at() const { return l.template at<T>(); }
-  template <int T>
-  __device__ __forceinline__ void prep() const {
-    if constexpr (T + 1 < 8) l.template pair<T + 1>();
-  }
-};
 
 template <int MODE>
 __device__ __forceinline__ void sigma_tile(State& s, const DensityArgs& d, float4* lds, float* clds, float* crow_lds,
@@ -1864,6 +2059,26 @@ int launch_field_w16_fold(int mode, FieldArgs& a, hipStream_t st) {
     case kFromPts: hipLaunchKernelGGL((w16::field_w16_kernel<kFromPts, false, false, true>), dim3(grid), b, 0, st, a); break;
     case kFromRayZ: hipLaunchKernelGGL((w16::field_w16_kernel<kFromRayZ, false, false, true>), dim3(grid), b, 0, st, a); break;
     default: hipLaunchKernelGGL((w16::field_w16_kernel<kFromEncoded, false, false, true>), dim3(grid), b, 0, st, a); break;
+  }
+  return cn::launch_status();
+}
+
+int launch_view_rows_w16(FieldArgs& a, float* rows, hipStream_t st) {
+  if (!a.fold_bias || !a.packed || !a.rd || !rows || a.n_rays <= 0) return CN_EINVAL;
+  const int64_t grid = cn::ceil_div(a.n_rays, w16::kVrRays);
+  if (grid > 0x7fffffff) return CN_EINVAL;
+  hipLaunchKernelGGL(w16::view_rows_kernel, dim3(static_cast<unsigned>(grid)), dim3(w16::kVrThreads), 0, st, a, rows);
+  return cn::launch_status();
+}
+
+int launch_field_w16_fold_rows(int mode, FieldArgs& a, hipStream_t st) {
+  if (!a.fold_bias || !a.view_rows || a.masks || a.save || a.n_codes != 1 || a.code_index) return CN_EINVAL;
+  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(a.m, w16::kTile), cu_count_w16()));
+  const dim3 b(w16::kThreads);
+  switch (mode) {
+    case kFromPts: hipLaunchKernelGGL((w16::field_w16_kernel<kFromPts, false, false, true, true>), dim3(grid), b, 0, st, a); break;
+    case kFromRayZ: hipLaunchKernelGGL((w16::field_w16_kernel<kFromRayZ, false, false, true, true>), dim3(grid), b, 0, st, a); break;
+    default: return CN_EINVAL;
   }
   return cn::launch_status();
 }

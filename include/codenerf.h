@@ -75,9 +75,11 @@ typedef void* cn_stream_t; /* hipStream_t */
  *                    feature rows folded into layer_dir1 (model.py:186-189 has no activation between
  *                    them): W_f = W_dir1[:, :256] W_out[1:, :256], each element a 256-term dot product
  *                    accumulated in double and rounded once.  28 weight chunks per tile instead of
- *                    36 (xyz1 2 | xyz2 8 | fold 8 | view-dir 1 | dir2 8 | rgb 1), 441,344 instead of
- *                    572,416 FLOP per sample; sigma_raw has CN_FMT_F32_W16's bits.  Read by
- *                    cn_mlp_forward_fold / cn_radiance_field_fold only, with cn_fold_bias's rows; every
+ *                    36 (xyz1 2 | xyz2 8 | view-dir 1 | fold 8 | dir2 8 | rgb 1: the view-direction
+ *                    chunk before W_f's, so what it adds depends on the ray alone and cn_view_rows can
+ *                    tabulate it), 441,344 instead of 572,416 FLOP per sample; sigma_raw has
+ *                    CN_FMT_F32_W16's bits.  Read by cn_mlp_forward_fold / cn_radiance_field_fold /
+ *                    cn_view_rows / cn_radiance_field_fold_rows only, with cn_fold_bias's rows; every
  *                    other entry point returns CN_EUNSUPPORTED for it.  No training or backward form
  *                    (their gradients need feat and fc_out's input gradient). */
 #define CN_FMT_F32_W16_FOLD 6
@@ -282,6 +284,39 @@ int cn_radiance_field_fold(const float* packed, int fmt, const float* code_bias,
                            const float* rd, const float* z, int64_t n_rays, int64_t n_samples,
                            int64_t chunk_rows, const float* freqs_xyz, const float* freqs_dir, float* raw,
                            cn_stream_t stream);
+
+/* Per-ray view-direction rows for cn_radiance_field_fold_rows.  Under Q1 (nerf/__init__.py:127-128) a
+ * sample takes the view direction of ray k mod Rc of its chunk, so a launch of n_rays rays holds only
+ * n_rays distinct directions, each used n_samples times; layer_dir1's view-direction term
+ * (model.py:188-189) is therefore per-ray work.  Row r (256 floats, feature order) =
+ * fold_bias row 0 + W_dir1[:, 256:] enc(rd[r] / |rd[r]|): bit for bit what cn_radiance_field_fold's
+ * kernel holds after its view-direction chunk (the same normalisation, sin / cos evaluator and
+ * matrix instructions in the same order).
+ * cn_view_rows_bytes(n_rays): the table's size, 1 KiB per ray (256 MiB for 262,144 rays), or -1 for
+ * n_rays <= 0 or a size past int64. */
+int64_t cn_view_rows_bytes(int64_t n_rays);
+
+/* Fill view_rows (cn_view_rows_bytes(n_rays) bytes, 16-byte aligned; every row written, nothing past
+ * them) from packed (the CN_FMT_F32_W16_FOLD pack), fold_bias (cn_fold_bias; row 0 is read) and the
+ * rays' directions rd (n_rays, 3).  freqs_dir (4): a HOST array.  One launch, 16 rays per wave.
+ * CN_EUNSUPPORTED for another valid fmt; CN_EINVAL, before any launch: a NULL pointer, n_rays <= 0,
+ * a misaligned packed / fold_bias / view_rows. */
+int cn_view_rows(const float* packed, int fmt, const float* fold_bias, const float* rd, int64_t n_rays,
+                 const float* freqs_dir, float* view_rows, cn_stream_t stream);
+
+/* cn_radiance_field_fold with the view-direction term read from view_rows (cn_view_rows of the same
+ * packed, fold_bias, rd, n_rays and freqs_dir) instead of computed per sample: the kernel neither
+ * normalises a direction nor encodes it, and streams 27 weight chunks per tile instead of 28.  raw is
+ * bit for bit cn_radiance_field_fold's for finite directions and frequencies inside the fast sin / cos
+ * range (|f| max|d| <= 16384); beyond them the two agree in which outputs are NaN.  One code row only:
+ * n_codes == 1 and code_index == NULL, anything else is CN_EINVAL.  A row costs one 1 KiB store and
+ * n_samples 1 KiB loads: on MI355X the table is even at 4 samples per ray and pays from 8 on; for
+ * single-sample lists use cn_radiance_field_fold. */
+int cn_radiance_field_fold_rows(const float* packed, int fmt, const float* code_bias, const float* fold_bias,
+                                const float* view_rows, const int64_t* code_index, int64_t n_codes,
+                                const float* pts, const float* ro, const float* rd, const float* z,
+                                int64_t n_rays, int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz,
+                                const float* freqs_dir, float* raw, cn_stream_t stream);
 
 /* Density alone: sigma_raw of CodeNeRFModel.forward, model.py:174-186 (layer_xyz1, layer_xyz2 with
  * the shape code, fc_out row 0) -- the first 10 of the field kernel's 36 weight chunks, 163,840 of
