@@ -110,6 +110,7 @@ SIGNATURES = {
     "cn_mlp_forward": (_i, [_p, _i, _p, _p, _i64, _p, _i64, _p, _p]),
     "cn_radiance_field": (_i, [_p, _i, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _fp, _fp, _p, _p]),
     "cn_density_field": (_i, [_p, _i, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _fp, _p, _p, _p]),
+    "cn_density_gradient": (_i, [_p, _p, _i, _i, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _fp, _p, _p]),
     "cn_occupancy_build": (_i, [_p, _i64, _f, _i, _p, _p]),
     "cn_occupancy_cull_workspace_bytes": (_i64, [_i64, _i64]),
     "cn_occupancy_cull": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _f, _f, _p, _p, _p, _p, _p, _p, _p]),

@@ -25,7 +25,8 @@ from .volumetric_render import volume_render
 
 __all__ = ["RaySampler", "PointSampler", "PositionalEmbedder", "volume_render", "prepare_samplers",
            "prepare_embedders", "predict_radiance_and_render", "forward_pass", "parallel_image_render",
-           "render_rays", "gather_rows", "gather_views", "density", "density_grid", "OccupancyGrid", "Mesh", "extract_mesh"]
+           "render_rays", "gather_rows", "gather_views", "density", "density_grid", "OccupancyGrid", "Mesh", "extract_mesh",
+           "density_gradient", "normals"]
 
 
 def prepare_samplers(cfg, height: int, width: int, intrinsics, datatype, device) -> Tuple[RaySampler, PointSampler]:
@@ -166,16 +167,98 @@ def density_grid(model, embedders, z_s: torch.Tensor, resolution: int, bound: fl
     return out.view(d, d, d)
 
 
+def _density_gradient_rows(model, embedders, cs, code_index, pts=None, ro=None, rd=None, z=None) -> torch.Tensor:
+    """ops.density_gradient of ``model`` on distinct shape code rows ``cs`` -> (.., 4) rows
+    [d sigma_raw / d point, sigma_raw], without gradients."""
+    from ..models.model import density_code_bias
+    fx, _ = _check_embedders(embedders)
+    m = _unwrap(model)
+    with torch.no_grad():
+        cb = density_code_bias(m, cs)
+        return ops.density_gradient(m.packed(), m.packed("f32_w16_t"), cb, fx, pts=pts, ro=ro, rd=rd, z=z,
+                                    code_index=code_index)
+
+
+def _activate_gradient(grad: torch.Tensor, sigma_raw: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(d sigma_raw / d p, sigma_raw) -> (d sigma / d p, sigma) of the density the renderer integrates,
+    sigma = softplus(sigma_raw - 1) (volumetric_render.py:32; torch's softplus, threshold 20):
+    d sigma / d sigma_raw = sigmoid(sigma_raw - 1)."""
+    x = sigma_raw - 1.0
+    return grad * torch.sigmoid(x)[..., None], torch.nn.functional.softplus(x)
+
+
+def _normals_from_gradient(g: torch.Tensor) -> torch.Tensor:
+    """n = -g / |g| in fp32: exactly (0, 0, 0) where |g| is 0, NaN in all three where a component of g is
+    not finite.  g is divided by its largest |component| first, so that the squares neither underflow (a
+    tiny gradient still has a unit normal) nor overflow."""
+    big = g.abs().amax(dim=-1, keepdim=True)
+    u = g / torch.where(big == 0, torch.ones_like(big), big)
+    n = torch.where(big == 0, torch.zeros_like(g), -u / torch.linalg.vector_norm(u, dim=-1, keepdim=True))
+    return torch.where(torch.isfinite(g).all(dim=-1, keepdim=True), n, torch.full_like(g, float("nan")))
+
+
+def _composite_normals(weights: torch.Tensor, n: torch.Tensor) -> torch.Tensor:
+    """sum_s w_s n_s over the samples of each ray, (R, S) x (R, S, 3) -> (R, 3); a sample of weight
+    exactly 0 contributes 0 whatever its normal (NaN included)."""
+    w = weights[..., None]
+    return torch.where(w == 0, torch.zeros_like(n), w * n).sum(dim=-2)
+
+
+def density_gradient(model, embedders, pts: torch.Tensor, z_s: torch.Tensor,
+                     activated: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The density's gradient with respect to the point, and the density, at points of any leading shape
+    (..., 3) for one shape code (1, 256) or one per row of the first dimension (pts.shape[0], 256) ->
+    (grad (..., 3), sigma (...)), from one kernel (ops.density_gradient).  ``activated``: of
+    softplus(sigma_raw - 1), the density the renderer integrates; else of sigma_raw, whose values are
+    bitwise ``density``'s.  Inference only."""
+    assert pts.shape[-1] == 3, "pts must be (..., 3)"
+    lead = tuple(pts.shape[:-1])
+    n = lead[0] if lead else 1
+    per_row = 1
+    for k in lead[1:]:
+        per_row *= k
+    assert z_s.dim() == 2 and z_s.shape[0] in (1, n), "z_s must be (1, C) or one row per pts.shape[0]"
+    with torch.no_grad():
+        if z_s.shape[0] > 1 and z_s.stride(0) == 0:
+            z_s = z_s[:1]
+        gs = _density_gradient_rows(model, embedders, z_s, None, pts=pts.detach().reshape(n, per_row, 3))
+        gs = gs.reshape(lead + (4,))
+        grad, sigma = gs[..., :3], gs[..., 3]
+        if activated:
+            grad, sigma = _activate_gradient(grad, sigma)
+    return grad, sigma
+
+
+def normals(model, embedders, pts: torch.Tensor, z_s: torch.Tensor) -> torch.Tensor:
+    """Unit normals of the density's level sets at ``pts`` (..., 3) -> (..., 3): -g / |g| of
+    density_gradient's g (towards lower density; the activation only scales g by a positive factor, so
+    sigma_raw's gradient is used), exactly (0, 0, 0) where |g| is 0 and NaN where g is not finite.
+    Inference only."""
+    with torch.no_grad():
+        return _normals_from_gradient(density_gradient(model, embedders, pts, z_s)[0])
+
+
+_point_normals = normals   # extract_mesh's and render_rays' keyword of the same name shadows the function there
+
+
 class Mesh:
     """A triangle mesh: ``vertices`` (V, 3) float32 and ``faces`` (T, 3) int32 (0-based vertex ids,
-    counter-clockwise seen from outside), on any device.  Saving copies them to the host."""
+    counter-clockwise seen from outside), optionally with per-vertex ``normals`` (V, 3) float32 and
+    ``colors`` (V, 3) float32 in [0, 1], on any device.  Saving copies them to the host."""
 
-    def __init__(self, vertices: torch.Tensor, faces: torch.Tensor):
+    def __init__(self, vertices: torch.Tensor, faces: torch.Tensor, *, normals: Optional[torch.Tensor] = None,
+                 colors: Optional[torch.Tensor] = None):
         if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
             raise ValueError(f"vertices must be (V, 3) float32, got {tuple(vertices.shape)} {vertices.dtype}")
         if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
             raise ValueError(f"faces must be (T, 3) int32, got {tuple(faces.shape)} {faces.dtype}")
-        self.vertices, self.faces = vertices, faces
+        for name, t in (("normals", normals), ("colors", colors)):
+            if t is not None and (t.dim() != 2 or tuple(t.shape) != tuple(vertices.shape) or t.dtype != torch.float32):
+                raise ValueError(f"{name} must be (V, 3) float32 with V = {vertices.shape[0]}, got "
+                                 f"{tuple(t.shape)} {t.dtype}")
+        if colors is not None and colors.numel() and not bool(((colors >= 0.0) & (colors <= 1.0)).all()):
+            raise ValueError("colors must lie in [0, 1]")
+        self.vertices, self.faces, self.normals, self.colors = vertices, faces, normals, colors
 
     @property
     def n_vertices(self) -> int:
@@ -188,40 +271,102 @@ class Mesh:
     def _host(self):
         return (self.vertices.detach().cpu().contiguous().numpy(), self.faces.detach().cpu().contiguous().numpy())
 
+    def _host_attrs(self):
+        return tuple(None if t is None else t.detach().cpu().contiguous().numpy() for t in (self.normals, self.colors))
+
     def save_obj(self, path: str) -> None:
-        """Wavefront OBJ text: ``v x y z`` (%.9g, which round-trips a float32) and ``f a b c``, 1-based."""
+        """Wavefront OBJ text: ``v x y z`` (%.9g, which round-trips a float32) and ``f a b c``, 1-based.
+        With colours: ``v x y z r g b`` (the common vertex-colour extension); with normals: a ``vn`` line
+        per vertex after the vertices and faces as ``f a//a b//b c//c``."""
         v, f = self._host()
+        nrm, col = self._host_attrs()
         with open(path, "w") as out:
-            out.writelines("v %.9g %.9g %.9g\n" % (float(x), float(y), float(z)) for x, y, z in v)
-            out.writelines("f %d %d %d\n" % (a + 1, b + 1, c + 1) for a, b, c in f.tolist())
+            if col is None:
+                out.writelines("v %.9g %.9g %.9g\n" % (float(x), float(y), float(z)) for x, y, z in v)
+            else:
+                out.writelines("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % tuple(float(t) for t in (*p, *c))
+                               for p, c in zip(v, col))
+            if nrm is None:
+                out.writelines("f %d %d %d\n" % (a + 1, b + 1, c + 1) for a, b, c in f.tolist())
+            else:
+                out.writelines("vn %.9g %.9g %.9g\n" % (float(x), float(y), float(z)) for x, y, z in nrm)
+                out.writelines("f %d//%d %d//%d %d//%d\n" % (a + 1, a + 1, b + 1, b + 1, c + 1, c + 1)
+                               for a, b, c in f.tolist())
 
     def save_ply(self, path: str) -> None:
-        """Binary little-endian PLY: float32 x, y, z per vertex; a uchar count (3) and int32 indices per face."""
+        """Binary little-endian PLY: float32 x, y, z per vertex, then float32 nx, ny, nz (with normals) and
+        uchar red, green, blue (with colours: round(c * 255), clamped); a uchar count (3) and int32 indices
+        per face."""
         import numpy as np
         v, f = self._host()
+        nrm, col = self._host_attrs()
+        props = "property float x\nproperty float y\nproperty float z\n"
+        fields = [("p", "<f4", (3,))]
+        if nrm is not None:
+            props += "property float nx\nproperty float ny\nproperty float nz\n"
+            fields.append(("n", "<f4", (3,)))
+        if col is not None:
+            props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+            fields.append(("c", "u1", (3,)))
         header = ("ply\nformat binary_little_endian 1.0\n"
-                  f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n"
+                  f"element vertex {v.shape[0]}\n{props}"
                   f"element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
+        verts = np.empty(v.shape[0], dtype=fields)
+        verts["p"] = v
+        if nrm is not None:
+            verts["n"] = nrm
+        if col is not None:
+            verts["c"] = np.clip(np.rint(col.astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
         rows = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
         rows["n"], rows["i"] = 3, f
         with open(path, "wb") as out:
             out.write(header.encode("ascii"))
-            out.write(v.astype("<f4").tobytes())
+            out.write(verts.tobytes())
             out.write(rows.tobytes())
 
 
 def extract_mesh(model, embedders, z_s: torch.Tensor, resolution: int, bound: float, level: float,
-                 activated: bool = True, max_points: int = 1 << 22) -> Mesh:
+                 activated: bool = True, max_points: int = 1 << 22, normals: bool = False, colors: bool = False,
+                 z_t: Optional[torch.Tensor] = None) -> Mesh:
     """The ``level`` iso-surface of one shape code's density as a triangle mesh, on the device:
     density_grid(resolution, bound, activated, max_points) followed by ops.isosurface with that grid's
     own ``linspace(-bound, bound, resolution)``, so every vertex lies on an edge of the sampled lattice.
-    ``level`` is in the grid's unit (activated density, or sigma_raw) and has no default; normals point
-    towards lower density.  Inference only; reads the vertex and face counts back once (a host
-    synchronisation, see ops.isosurface).  No vertex normals, simplification or colours."""
+    ``level`` is in the grid's unit (activated density, or sigma_raw) and has no default; face normals
+    point towards lower density.  Inference only; reads the vertex and face counts back once (a host
+    synchronisation, see ops.isosurface).  No simplification.
+    ``normals``: ``Mesh.normals`` = ``normals(model, embedders, vertices, z_s)``, the density's own
+    gradient direction at each vertex (not an average of face normals).
+    ``colors`` (needs the texture code ``z_t`` (1, 256); computes the normals too): ``Mesh.colors`` =
+    sigmoid of the colour channels of the model's no-grad field at the vertices, each seen along
+    rd = -normal (the ray travels into the surface; (0, 0, -1) where the normal is zero or not finite).
+    Vertices and faces are those of the plain call."""
+    if colors and z_t is None:
+        raise ValueError("colors=True needs the texture code z_t (1, C)")
     d = int(resolution)
     nodes = density_grid(model, embedders, z_s, d, bound, activated=activated, max_points=max_points)
     lin = torch.linspace(-bound, bound, d, dtype=torch.float32, device=nodes.device)
-    return Mesh(*ops.isosurface(nodes, level, lin))
+    vertices, faces = ops.isosurface(nodes, level, lin)
+    if not (normals or colors):
+        return Mesh(vertices, faces)
+    nrm = _point_normals(model, embedders, vertices, z_s)
+    col = None
+    if colors:
+        col = _vertex_colors(model, embedders, vertices, nrm, z_s, z_t)
+    return Mesh(vertices, faces, normals=nrm, colors=col)
+
+
+def _vertex_colors(model, embedders, vertices, nrm, z_s, z_t) -> torch.Tensor:
+    """sigmoid(raw[..., :3]) of ``model``'s inference field at ``vertices`` (V, 3), one sample per ray,
+    viewed along -``nrm`` ((0, 0, -1) where the normal is zero or not finite) -> (V, 3) in [0, 1]."""
+    v = vertices.shape[0]
+    if v == 0:
+        return torch.empty(0, 3, dtype=torch.float32, device=vertices.device)
+    with torch.no_grad():
+        usable = torch.isfinite(nrm).all(dim=-1, keepdim=True) & (nrm != 0).any(dim=-1, keepdim=True)
+        down = torch.tensor([0.0, 0.0, -1.0], dtype=torch.float32, device=vertices.device).expand(v, 3)
+        rd = torch.where(usable, -nrm, down).contiguous()
+        raw = _field(model, embedders, rd, z_s.detach(), z_t.detach(), chunk_rows=v, pts=vertices.view(v, 1, 3))
+        return torch.sigmoid(raw[:, 0, :3])
 
 
 class OccupancyGrid:
@@ -338,7 +483,7 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
                 t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
                 coarse_only: bool = False, events: Optional[dict] = None,
                 coarse_rgb: bool = True, occupancy: Optional[OccupancyGrid] = None,
-                rgb_tolerance: Optional[float] = None) -> Dict[str, torch.Tensor]:
+                rgb_tolerance: Optional[float] = None, normals: bool = False) -> Dict[str, torch.Tensor]:
     """predict_radiance_and_render over a whole ray list, chunk semantics kept via ``chunk_rows``.
 
     Returns rgb/depth/acc for the coarse pass (+ weights) and, unless
@@ -364,7 +509,16 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     "rgb_fine" is within 0.501 x (the ray's culled weight, <= tol) of it, plus fp32 summation rounding.
     0.0 culls only samples of weight 0 or NaN.  Composes with ``occupancy``.  The kept count is read
     back on the host once (ops.weight_cull), so this render is not graph-capturable either.
+    ``normals`` (inference only; needs a fine pass): adds "normal_fine" (R, 3) = sum_s w_s n_s, w the fine
+    pass's compositing weights and n_s the unit normals (``normals``' rule) of the fine model's density at
+    the fine samples, from one ops.density_gradient launch over (ro, rd, z_fine).  Not normalised: its
+    length is at most "acc_fine".  A sample of weight exactly 0 -- every culled one -- contributes 0 even
+    where its normal is NaN.  Every other entry is bitwise the call's without ``normals``; composes with
+    ``occupancy`` and ``rgb_tolerance`` (the gradient kernel still runs over every fine sample).
     """
+    if normals and (coarse_only or fine_model is None):
+        raise ValueError("normals=True composites the fine pass's normals: there is no fine pass with "
+                         "coarse_only=True (or without a fine model)")
     if rgb_tolerance is not None:
         rgb_tolerance = float(rgb_tolerance)
         if not rgb_tolerance >= 0.0:
@@ -372,7 +526,7 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
         if coarse_only or fine_model is None:
             raise ValueError("rgb_tolerance bounds the fine pass's colours: there is none to apply it to with "
                              "coarse_only=True (or without a fine model)")
-    if not coarse_rgb or occupancy is not None or rgb_tolerance is not None:
+    if not coarse_rgb or occupancy is not None or rgb_tolerance is not None or normals:
         if torch.is_grad_enabled() and (
                 any(t is not None and t.requires_grad for t in (ro, rd, z_s, z_t)) or
                 any(p.requires_grad for m in (coarse_model, fine_model) if m is not None
@@ -380,6 +534,9 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
             if rgb_tolerance is not None:
                 raise ValueError("rgb_tolerance is an inference render: the two-phase fine pass has no backward "
                                  "(render under torch.no_grad(), or pass rgb_tolerance=None)")
+            if normals:
+                raise ValueError("normals=True is an inference render: the density-gradient kernel has no "
+                                 "backward (render under torch.no_grad(), or pass normals=False)")
             if coarse_rgb:
                 raise ValueError("occupancy culling is an inference render: the compacted field has no backward "
                                  "(render under torch.no_grad(), or pass occupancy=None)")
@@ -441,8 +598,13 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     _, z_f = ops.sample_pdf(ro.detach(), rd.detach(), w_c.detach()[..., 1:-1], z_c, ps.num_samples_fine,
                             u if ps.perturb else ps.u_lin, want_pts=False)
     raw_f = timed_field(fine_model, embedders, rd, z_s, z_t, chunk_rows, ro=ro, z=z_f, pair=pair, field=fine_field)
-    rgb_f, disp_f, acc_f, _, depth_f = volume_render(raw_f, z_f, rd)
+    rgb_f, disp_f, acc_f, w_f, depth_f = volume_render(raw_f, z_f, rd)
     out.update({"rgb_fine": rgb_f, "disp_fine": disp_f, "acc_fine": acc_f, "depth_fine": depth_f, "z_fine": z_f})
+    if normals:
+        cs, _, code_index = _codes(z_s, z_t)
+        with torch.no_grad():
+            gs = _density_gradient_rows(fine_model, embedders, cs, code_index, ro=ro.detach(), rd=rd.detach(), z=z_f)
+            out["normal_fine"] = _composite_normals(w_f, _normals_from_gradient(gs[..., :3]))
     return out
 
 

@@ -568,6 +568,48 @@ def density_field(packed: Tensor, cb: Tensor, freqs_xyz: Sequence[float], *, pts
     return sigma if want_sigma else raw
 
 
+def density_gradient(packed: Tensor, packed_t: Tensor, cb: Tensor, freqs_xyz: Sequence[float], *,
+                     pts: Optional[Tensor] = None, ro: Optional[Tensor] = None, rd: Optional[Tensor] = None,
+                     z: Optional[Tensor] = None, code_index: Optional[Tensor] = None) -> Tensor:
+    """d sigma_raw / d point and sigma_raw in one launch (cn_density_gradient) -> (.., 4) rows
+    [d/dx, d/dy, d/dz, sigma_raw]: column 3 is bitwise density_field's sigma, columns 0..2 equal the d_pts
+    of radiance_field_masks + field_backward_x3(precision="f32") on d_raw = (0, 0, 0, 1).
+
+    Exactly one input: ``pts`` (R, S, 3) or (M, 3) [R = M, S = 1]; ``ro``, ``rd`` (R, 3) with ``z`` (R, S):
+    the gradient is taken at ro + rd z, with respect to that point.  ``packed``: the "f32_w16" pack,
+    ``packed_t``: the "f32_w16_t" pack of the same parameters; ``cb`` one code row, one per R, or rows picked
+    by ``code_index`` (R,)."""
+    lib = _lib_ready()
+    modes = (pts is not None) + (ro is not None or rd is not None or z is not None)
+    assert modes == 1, "give exactly one of pts and (ro, rd, z)"
+    if pts is not None:
+        pts = _cuda(pts, "pts")
+        assert pts.dim() in (2, 3) and pts.shape[-1] == 3, "pts must be (num_rays, num_samples, 3) or (M, 3)"
+        lead = tuple(pts.shape[:-1])
+        dev = pts.device
+    else:
+        assert ro is not None and rd is not None and z is not None, "the ray form takes ro, rd and z"
+        ro, rd, z = _cuda(ro, "ro"), _cuda(rd, "rd"), _cuda(z, "z")
+        assert z.dim() == 2 and ro.shape == (z.shape[0], 3) and rd.shape == (z.shape[0], 3), \
+            "ro / rd must be (num_rays, 3) and z (num_rays, num_samples)"
+        lead, dev = tuple(z.shape), z.device
+    n = lead[0]
+    s = lead[1] if len(lead) == 2 else 1
+    n_codes = cb.shape[0]
+    if code_index is not None:
+        code_index = _cuda(code_index, "code_index", torch.int64)
+        assert code_index.shape == (n,), "code_index must be (num_rays,)"
+    else:
+        assert n_codes in (1, n), "codes must be one row or one row per ray"
+    assert len(freqs_xyz) == 10, "the field kernel implements L_xyz=10"
+    out = torch.empty(lead + (4,), device=dev, dtype=torch.float32)
+    if n * s:      # no samples: an empty output without a launch (the C ABI refuses sizes of 0)
+        check(lib.cn_density_gradient(ptr(packed), ptr(packed_t), _lib.CN_FMT_F32_W16, _lib.CN_FMT_F32_W16_T, ptr(cb),
+                                      ptr(code_index), n_codes, ptr(pts), ptr(ro), ptr(rd), ptr(z), n, s,
+                                      _lib.host_floats(freqs_xyz), ptr(out), stream_of(cb)), "cn_density_gradient")
+    return out
+
+
 # ------------------------------------------------------------------ occupancy-grid culling
 
 

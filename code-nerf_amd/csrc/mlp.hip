@@ -644,6 +644,41 @@ extern "C" int cn_density_field(const float* packed, int fmt, const float* code_
   return launch_density_w16(pts ? kFromPts : (x ? kFromEncoded : kFromRayZ), d, cn::as_stream(stream));
 }
 
+extern "C" int cn_density_gradient(const float* packed, const float* packed_t, int fmt, int fmt_t,
+                                   const float* code_bias, const int64_t* code_index, int64_t n_codes,
+                                   const float* pts, const float* ro, const float* rd, const float* z, int64_t n_rays,
+                                   int64_t n_samples, const float* freqs_xyz, float* grad_sigma,
+                                   cn_stream_t stream) {
+  CN_CHECK_ARG(packed && packed_t && code_bias && freqs_xyz && grad_sigma);
+  const bool rays = ro || rd || z;
+  CN_CHECK_ARG((pts ? 1 : 0) + (rays ? 1 : 0) == 1);  // exactly one input mode
+  CN_CHECK_ARG(!rays || (ro && rd && z));
+  CN_CHECK_ARG(cn::aligned16(grad_sigma));  // float4 rows (include/codenerf.h)
+  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && n_codes > 0);
+  CN_CHECK_ARG(n_rays <= INT64_MAX / n_samples && cn::ceil_div(n_rays * n_samples, kTile) <= 0x7fffffff);
+  CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == n_rays);
+  // fmt a forward format, fmt_t a transposed one (the two swapped, or an unknown value: invalid)
+  CN_CHECK_ARG(valid_fmt(fmt) || fmt == CN_FMT_F32_W16_FOLD);
+  CN_CHECK_ARG(fmt_t == CN_FMT_BF16X3_T || fmt_t == CN_FMT_F32_W16_T);
+  if (fmt != CN_FMT_F32_W16 || fmt_t != CN_FMT_F32_W16_T) return CN_EUNSUPPORTED;
+  DensityArgs d = {};
+  d.f.packed = packed;
+  d.f.code_bias = code_bias;
+  d.f.code_index = code_index;
+  d.f.n_codes = n_codes;
+  d.f.pts = pts;
+  d.f.ro = ro;
+  d.f.rd = rd;
+  d.f.z = z;
+  d.f.n_rays = n_rays;
+  d.f.n_samples = n_samples;
+  d.f.chunk_rows = n_rays;
+  d.f.m = n_rays * n_samples;
+  for (int i = 0; i < 10; ++i) d.f.fx[i] = freqs_xyz[i];
+  d.f.raw = grad_sigma;
+  return launch_density_grad_w16(pts ? kFromPts : kFromRayZ, d, packed_t, cn::as_stream(stream));
+}
+
 extern "C" int cn_radiance_field_train(const float* packed, const float* code_bias, const int64_t* code_index,
                                        int64_t n_codes, const float* pts, const float* ro, const float* rd,
                                        const float* z, int64_t n_rays, int64_t n_samples, int64_t chunk_rows,

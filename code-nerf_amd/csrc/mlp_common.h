@@ -307,6 +307,9 @@ int64_t packed_floats_w16();
 int launch_pack_w16(const Params& P, float* packed, hipStream_t st);
 int launch_field_w16(int mode, FieldArgs& a, hipStream_t st);  // a.masks: also the ReLU masks
 int launch_density_w16(int mode, DensityArgs& d, hipStream_t st);  // sigma only: the stream's first 10 chunks
+// d sigma_raw / d point and sigma_raw as (m, 4) rows in d.f.raw: the forward pack's first 10 chunks,
+// then the last 10 of the transposed pack packed_t (points or rays; no encoded mode)
+int launch_density_grad_w16(int mode, DensityArgs& d, const float* packed_t, hipStream_t st);
 int64_t mask_words_w16(int64_t m);
 // the folded inference form (fc_out's feature rows folded into layer_dir1): its pack, the per-code
 // c_v1 rows and the forward on them (a.fold_bias; no masks, no planes)

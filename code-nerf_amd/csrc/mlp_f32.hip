@@ -247,6 +247,7 @@ struct State {
   int crow;          // this lane's code-bias row
   bool uniform_code; // all 16 samples of the wave use one code row
   __amdgpu_buffer_rsrc_t wsrc;
+  __amdgpu_buffer_rsrc_t wsrc_t;  // density-gradient kernel: the transposed pack (kStreamGrad)
   unsigned voff;
   unsigned poff;     // this lane's byte offset in a (kTile, 256) fp32 plane block: row 16 wave + (lane & 15), col 4 g
   unsigned gbase;    // backward: this lane's byte offset in a 256-float sum row (rowsum64's features)
@@ -329,17 +330,31 @@ __device__ __forceinline__ int stream_src_rows(const State& s, int cn) {
   return k + (k >= kFDir ? 1 : 0);
 }
 
+// kStreamGrad: the density-gradient kernel's 20 chunks from cn = 0 in every tile -- the forward pack's
+// first kSigmaChunks (layer_xyz1, layer_xyz2), then the transposed pack's last kSigmaChunks from
+// kGradTFirst (layer_xyz2^T, layer_xyz1^T), through that pack's own buffer resource (s.wsrc_t).
+constexpr int kStreamGrad = 5, kGradChunks = 2 * kSigmaChunks, kGradTFirst = kChunks - kSigmaChunks;
+static_assert(kGradChunks % kRing == 0, "cyclic stream: chunk c + 20 reuses chunk c's ring slot");
+
 // One LDS-DMA piece: 1 KiB of chunk cn (piece p of 4 for this wave).
 template <int NG = kStreamFull>
 __device__ __forceinline__ void dma_piece(const State& s, float4* lds, int cn, int p) {
-  const int src = NG == kStreamSigma ? stream_src_sigma(s, cn)
-                  : NG == kStreamNG  ? stream_src_ng(s, cn)
-                  : NG == kStreamFold ? (cn < kFoldChunks ? cn : cn - kFoldChunks)
-                  : NG == kStreamRows ? stream_src_rows(s, cn)
-                                     : (cn < kChunks ? cn : cn - kChunks);
+  int src = NG == kStreamSigma ? stream_src_sigma(s, cn)
+            : NG == kStreamNG  ? stream_src_ng(s, cn)
+            : NG == kStreamFold ? (cn < kFoldChunks ? cn : cn - kFoldChunks)
+            : NG == kStreamRows ? stream_src_rows(s, cn)
+            : NG == kStreamGrad ? (cn < kGradChunks ? cn : cn - kGradChunks)
+                               : (cn < kChunks ? cn : cn - kChunks);
+  __amdgpu_buffer_rsrc_t rsrc = s.wsrc;
+  if constexpr (NG == kStreamGrad) {
+    if (src >= kSigmaChunks) {  // wave-uniform: cn is
+      src += kGradTFirst - kSigmaChunks;
+      rsrc = s.wsrc_t;
+    }
+  }
   const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(src * kChunkQuads + p * 64 * kWaves) * 16u);
   __builtin_amdgcn_raw_ptr_buffer_load_lds(
-      s.wsrc, (lds_ptr_t)(lds + (cn & (kRing - 1)) * kChunkQuads + p * 64 * kWaves + s.wave * 64), 16, s.voff,
+      rsrc, (lds_ptr_t)(lds + (cn & (kRing - 1)) * kChunkQuads + p * 64 * kWaves + s.wave * 64), 16, s.voff,
       soff, 0, 0);
 }
 
@@ -1181,18 +1196,28 @@ constexpr int kSigLdsQuads = kRing * kChunkQuads + (kLdsConsts + kWaves * 256) /
 static_assert(kSigLdsQuads * 16 <= 160 * 1024, "LDS budget (density)");
 static_assert((2 * kSigmaChunks) % kRing == 0, "the density counter folds mod 2 tiles");
 
-template <int MODE>
-__device__ __forceinline__ void sigma_tile(State& s, const DensityArgs& d, float4* lds, float* clds, float* crow_lds,
-                                          int64_t tile, int& c) {
-  const FieldArgs& a = d.f;
-  const int64_t row = tile * kTile + s.wave * 16 + (s.lane & 15);
-  const bool valid = row < a.m;
-  const int64_t rc = valid ? row : a.m - 1;
-  s.cbase = c;
+// Mask words kept in registers for a backward in the same kernel, as values the compiler cannot see
+// through: otherwise mask_act's bit tests become the 128 compare results themselves, held in SGPR
+// pairs (and spilled) from the forward to the backward.
+template <bool MASKS>
+__device__ __forceinline__ uint2v opaque_mask(uint2v w) {
+  if constexpr (MASKS) {
+    w[0] = static_cast<unsigned>(fresh(static_cast<int>(w[0])));
+    w[1] = static_cast<unsigned>(fresh(static_cast<int>(w[1])));
+  }
+  return w;
+}
 
+// The forward of sample row rc through chunks c .. c + 9 of stream NG; returns sigma_raw (every lane
+// group holds it).  x: the point (left as it is in kFromEncoded); MASKS: the ReLU mask words of h1 and h2
+// (relu_act) into m_h1, m_h2 -- the density-gradient kernel's backward reads both.
+template <int MODE, int NG = kStreamSigma, bool MASKS = false>
+__device__ __forceinline__ float sigma_forward(State& s, const DensityArgs& d, float4* lds, float* clds,
+                                              float* crow_lds, int64_t rc, int& c, float (&x)[3], uint2v& m_h1,
+                                              uint2v& m_h2) {
+  const FieldArgs& a = d.f;
   // ---- the point (decode_sample's formulas), the code row and its layer_xyz2 / sigma terms
   const int64_t ray = rc / a.n_samples;
-  float x[3] = {0.0f, 0.0f, 0.0f};
   if constexpr (MODE == kFromPts) {
     x[0] = a.pts[3 * rc]; x[1] = a.pts[3 * rc + 1]; x[2] = a.pts[3 * rc + 2];
   } else if constexpr (MODE == kFromRayZ) {
@@ -1244,8 +1269,8 @@ __device__ __forceinline__ void sigma_tile(State& s, const DensityArgs& d, float
       const LazyXyzOnly l0{LazyXyz{enc, s.denc, x, x, fr, g, false}};
       l0.l.pair<0>();
       bias_from(s, clds + kCB1);
-      chunk16<8, 0, kStreamSigma>(s, lds, c + 0, l0);
-      chunk16<8, 0, kStreamSigma>(s, lds, c + 1, ArrB<8>{enc});
+      chunk16<8, 0, NG>(s, lds, c + 0, l0);
+      chunk16<8, 0, NG>(s, lds, c + 1, ArrB<8>{enc});
     }
   } else {
     if constexpr (MODE != kFromEncoded) {
@@ -1266,24 +1291,37 @@ __device__ __forceinline__ void sigma_tile(State& s, const DensityArgs& d, float
       }
     }
     bias_from(s, clds + kCB1);
-    chunk16<8, 0, kStreamSigma>(s, lds, c + 0, ArrB<0>{enc});
-    chunk16<8, 0, kStreamSigma>(s, lds, c + 1, ArrB<8>{enc});
+    chunk16<8, 0, NG>(s, lds, c + 0, ArrB<0>{enc});
+    chunk16<8, 0, NG>(s, lds, c + 1, ArrB<8>{enc});
   }
   c += 2;
 
   // ---- layer_xyz2
-  relu_act<false>(s);
+  m_h1 = opaque_mask<MASKS>(relu_act<MASKS>(s));
   static_assert(kCbXyz2 == 0, "crow_lds holds the code-bias row's first 256 floats");
   bias_code(s, a, crow_lds, kCbXyz2);
   __builtin_amdgcn_sched_barrier(0);
-  layer256<kStreamSigma>(s, lds, c);
+  layer256<NG>(s, lds, c);
 
   // ---- sigma
-  relu_act<false>(s);
+  m_h2 = opaque_mask<MASKS>(relu_act<MASKS>(s));
   float sg = sigma_partial(s, clds);
   sg += __shfl_xor(sg, 16);
   sg += __shfl_xor(sg, 32);
-  sg += bs;
+  return sg + bs;
+}
+
+template <int MODE>
+__device__ __forceinline__ void sigma_tile(State& s, const DensityArgs& d, float4* lds, float* clds, float* crow_lds,
+                                          int64_t tile, int& c) {
+  const FieldArgs& a = d.f;
+  const int64_t row = tile * kTile + s.wave * 16 + (s.lane & 15);
+  const bool valid = row < a.m;
+  const int64_t rc = valid ? row : a.m - 1;
+  s.cbase = c;
+  float x[3] = {0.0f, 0.0f, 0.0f};
+  uint2v m_h1, m_h2;
+  const float sg = sigma_forward<MODE>(s, d, lds, clds, crow_lds, rc, c, x, m_h1, m_h2);
   if (valid && s.g == 0) {
     if (d.sigma) d.sigma[row] = sg;
     if (a.raw) reinterpret_cast<float4*>(a.raw)[row] = make_float4(0.0f, 0.0f, 0.0f, sg);
@@ -1355,6 +1393,7 @@ constexpr int kBwdLdsFloats = kBGacc + kWaves * kCbStride;
 constexpr int kBwdLdsQuads = kRing * kChunkQuads + kBwdLdsFloats / 4;
 static_assert(kBwdLdsQuads * 16 <= 160 * 1024, "LDS budget (backward)");
 static_assert(kTXyz1 + 2 == kChunks, "backward chunk schedule");
+static_assert(kGradTFirst == kTXyz2, "the density-gradient stream's second half: layer_xyz2^T, layer_xyz1^T");
 static_assert(kTDDir == kNoGeoSkip && kTDDir + 1 == kTOut, "no-geometry stream: skips the view-dir chunk");
 
 // Elements idx0, idx0 + stride, ... of the CN_FMT_F32_W16_T pack (pack_w16t_kernel; a role of
@@ -1593,7 +1632,7 @@ __device__ __forceinline__ void mfma_narrow(State& s, const floatx4* a) {
 }
 
 // A narrow chunk (2 blocks x 64 k-steps, B from s.act) into s.acc2, on chunk16's schedule.
-template <int CI = 0, typename Post = NoPost>
+template <int CI = 0, int NG = kStreamFull, typename Post = NoPost>
 __device__ __forceinline__ void chunk_narrow(State& s, float4* lds, int c, Post post = Post{}) {
   const float4* slot = lds + (c & (kRing - 1)) * kChunkQuads + s.lane;
   const float4* nslot = lds + ((c + 1) & (kRing - 1)) * kChunkQuads + s.lane;
@@ -1610,7 +1649,7 @@ __device__ __forceinline__ void chunk_narrow(State& s, float4* lds, int c, Post 
     __builtin_amdgcn_sched_barrier(0);                              \
     if constexpr ((T) == 3) {                                       \
       chunk_barrier();                                              \
-      dma_chunk(s, lds, c + 3);                                     \
+      dma_chunk<NG>(s, lds, c + 3);                                 \
     }                                                               \
     post.template step<CI, (T)>();                                  \
   }
@@ -1623,6 +1662,37 @@ __device__ __forceinline__ void chunk_narrow(State& s, float4* lds, int c, Post 
   CN_NSTEP(6, a0, a1)
   CN_NSTEP(7, a1, a0)
 #undef CN_NSTEP
+}
+
+// d enc -> d point (every lane group ends with the sample's sum): lane group g owns pairs p = 4 i + g
+// (as the forward); genc = its layer_xyz1^T outputs in the forward's encoding k-step order.  The
+// operations and their order are bwd_tile's "encodings -> d pts" block, which the density-gradient
+// kernel's result is compared against value for value.
+__device__ __forceinline__ void enc_backward(const State& s, const float (&x)[3], const float (&genc)[16],
+                                             const float* clds, float (&dx)[3]) {
+  dx[0] = dx[1] = dx[2] = 0.f;
+  const int g = fresh(s.g);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int p = 4 * i + g;
+    if (p < 30) {
+      const int d = p % 3, k = p / 3;
+      float sn, cs;
+      const float f = clds[kCFreq + k];
+      sincosf(__fmul_rn(pick3(x, d), f), &sn, &cs);
+      add3(dx, d, f * (genc[i] * cs - genc[8 + i] * sn));
+    } else if (g == 2) {  // raw inputs x0 (k-step 7), x1 (k-step 15)
+      dx[0] += genc[7];
+      dx[1] += genc[15];
+    } else {                // x2 (k-step 7)
+      dx[2] += genc[7];
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    dx[d] += __shfl_xor(dx[d], 16);
+    dx[d] += __shfl_xor(dx[d], 32);
+  }
 }
 
 // Flush this wave's g_code row (LDS) into g_code[code] and zero it.
@@ -1834,6 +1904,8 @@ __device__ __forceinline__ void bwd_tile(State& s, const FieldArgs& a, float4* l
   }
 
   // ---- encodings -> d pts: lane group g owns pairs p = 4 i + g (as the forward)
+  // (enc_backward is this block as a function, for the density-gradient kernel; it stays in line here
+  // because this kernel sits at the register cap and the call changed its register allocation)
   float dx[3] = {0.f, 0.f, 0.f};
   const int g = fresh(s.g);
 #pragma unroll
@@ -1993,6 +2065,111 @@ __global__ __launch_bounds__(kThreads, 2) void field_w16_bwd2_kernel(FieldArgs a
   else bwd_body<MODE, TRAIN, NOGEO, DET>(a0, lds, blockIdx.x, first1);
 }
 
+
+// ================================================================ density gradient
+// d sigma_raw / d point and sigma_raw in one launch (cn_density_gradient): the density kernel's
+// forward with both ReLU masks kept in registers, then the fused backward's tail from
+// mask_act(m_h2) on with d sigma = 1 -- what the composed path (the field forward writing masks, then
+// the whole fused backward on d raw = (0, 0, 0, 1)) computes, without its 26 + 26 chunks that only add
+// exact zeros and without the masks' trip through memory.  Chunk schedule per tile (kStreamGrad,
+// c = 0 at every tile: 20 chunks, the ring is cyclic):
+//   0, 1     layer_xyz1     forward pack 0, 1      B = the xyz encodings (lazy or up front, per wave)
+//   2 .. 9   layer_xyz2     forward pack 2 .. 9    B = relu(h1) -> m_h1; accumulators from kCbXyz2
+//   epilogue relu -> m_h2, sigma_partial + butterfly + code_bias[kCbSigma]   (the density kernel's bits)
+//            d h2 = m_h2 . fc_out row 0 (the transposed pack's kTSig constants; fc_out^T over the
+//            all-zero d feat is skipped: it adds zeros)
+//   10 .. 17 layer_xyz2^T   transposed pack 26 .. 33   B = d h2
+//   18, 19   layer_xyz1^T   transposed pack 34, 35     B = m_h1 . d h1 (narrow chunks) -> d enc
+//   epilogue d enc -> d point (enc_backward), one float4 store per sample
+// Chunks 17 .. 19 fetch the next tile's chunks 0 .. 2; chunk 19's last k-step pre-reads its first A
+// fragments.
+// LDS after the ring: the forward constants, fc_out row 0 from the transposed pack, then the
+// layer_xyz2 code-bias vector per wave.
+struct DensityGradArgs {
+  DensityArgs d;          // d.f.raw: the (m, 4) output; d.sigma unused
+  const float* packed_t;  // CN_FMT_F32_W16_T
+};
+constexpr int kGradTSig = kLdsConsts, kGradCrow = kGradTSig + 256;
+constexpr int kGradLdsQuads = kRing * kChunkQuads + (kGradCrow + kWaves * 256) / 4;
+static_assert(kGradLdsQuads * 16 <= 160 * 1024, "LDS budget (density gradient)");
+
+template <int MODE>
+__device__ __forceinline__ void grad_tile(State& s, const DensityArgs& d, float4* lds, float* clds, float* crow_lds,
+                                         int64_t tile) {
+  static_assert(MODE != kFromEncoded, "no point to differentiate against");
+  const FieldArgs& a = d.f;
+  const int64_t row = tile * kTile + s.wave * 16 + (s.lane & 15);
+  const bool valid = row < a.m;
+  const int64_t rc = valid ? row : a.m - 1;
+  int c = 0;
+
+  // ---- forward: sigma_raw and the two masks
+  float x[3];
+  uint2v w_h1, w_h2;
+  const float sg = sigma_forward<MODE, kStreamGrad, true>(s, d, lds, clds, crow_lds, rc, c, x, w_h1, w_h2);
+  const uint2 m_h1 = make_uint2(w_h1[0], w_h1[1]), m_h2 = make_uint2(w_h2[0], w_h2[1]);
+
+  // ---- layer_xyz2^T: B = d h2 = m_h2 . fc_out row 0 (d sigma = 1)
+#pragma unroll
+  for (int ob = 0; ob < 16; ++ob)
+    s.acc[ob] = *reinterpret_cast<const floatx4*>(clds + kGradTSig + 64 * fresh(s.g) + 4 * ob);
+  mask_act(s, m_h2);
+  zero_acc(s);
+  __builtin_amdgcn_sched_barrier(0);
+  layer256<kStreamGrad>(s, lds, c);
+  // ---- layer_xyz1^T (m_h1): encoding k-steps 0-7, then 8-15
+  mask_act(s, m_h1);
+  float genc[16];
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s.acc2[q] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
+    chunk_narrow<0, kStreamGrad>(s, lds, c);
+    c += 1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      genc[8 * half + r] = s.acc2[0][r] + s.acc2[1][r];
+      genc[8 * half + 4 + r] = s.acc2[2][r] + s.acc2[3][r];
+    }
+  }
+  float dx[3];
+  enc_backward(s, x, genc, clds, dx);
+  if (valid && s.g == 0) reinterpret_cast<float4*>(a.raw)[row] = make_float4(dx[0], dx[1], dx[2], sg);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kThreads, 2) void density_grad_w16_kernel(DensityGradArgs ga) {
+  // one LDS object, as field_w16_kernel
+  __shared__ __attribute__((aligned(16))) float4 lds[kGradLdsQuads];
+  float* clds = reinterpret_cast<float*>(lds + kRing * kChunkQuads);
+  const DensityArgs& d = ga.d;
+  State s;
+  s.lane = threadIdx.x & 63;
+  s.g = s.lane >> 4;
+  s.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  s.wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.f.packed), 0, kPackedFloats * 4, 0x00020000);
+  s.wsrc_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ga.packed_t), 0, kPackedFloats * 4, 0x00020000);
+  s.voff = static_cast<unsigned>(s.wave * 64 + s.lane) * 16u;
+  s.cbase = 0;
+  float* crow_lds = clds + kGradCrow + s.wave * 256;
+
+  load_consts(d.f, clds);
+  if (threadIdx.x < 256) clds[kGradTSig + threadIdx.x] = ga.packed_t[kStreamFloats + kTSig + threadIdx.x];
+  dma_chunk<kStreamGrad>(s, lds, 0);
+  dma_chunk<kStreamGrad>(s, lds, 1);
+  dma_chunk<kStreamGrad>(s, lds, 2);
+  asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  read_a<0>(lds + s.lane, s.pre);
+
+  const int64_t n_tiles = (d.f.m + kTile - 1) / kTile;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
+    grad_tile<MODE>(s, d, lds, clds, crow_lds, tile);
+  // the last tile prefetched three chunks of a tile that does not exist: they must land before
+  // the workgroup's LDS is released
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+}
+
 }  // namespace w16
 
 static int64_t cu_count_w16() {
@@ -2091,6 +2268,16 @@ int launch_density_w16(int mode, DensityArgs& d, hipStream_t st) {
     case kFromRayZ: hipLaunchKernelGGL((w16::density_w16_kernel<kFromRayZ>), dim3(grid), b, 0, st, d); break;
     default: hipLaunchKernelGGL((w16::density_w16_kernel<kFromEncoded>), dim3(grid), b, 0, st, d); break;
   }
+  return cn::launch_status();
+}
+
+int launch_density_grad_w16(int mode, DensityArgs& d, const float* packed_t, hipStream_t st) {
+  if (mode != kFromPts && mode != kFromRayZ) return CN_EINVAL;
+  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(d.f.m, w16::kTile), cu_count_w16()));
+  const dim3 b(w16::kThreads);
+  const w16::DensityGradArgs ga{d, packed_t};
+  if (mode == kFromPts) hipLaunchKernelGGL((w16::density_grad_w16_kernel<kFromPts>), dim3(grid), b, 0, st, ga);
+  else hipLaunchKernelGGL((w16::density_grad_w16_kernel<kFromRayZ>), dim3(grid), b, 0, st, ga);
   return cn::launch_status();
 }
 

@@ -341,6 +341,32 @@ int cn_density_field(const float* packed, int fmt, const float* code_bias, const
                      const float* x, int64_t x_stride, int64_t n_rays, int64_t n_samples,
                      const float* freqs_xyz, float* sigma, float* raw, cn_stream_t stream);
 
+/* The density's gradient: grad_sigma (m, 4) rows [d sigma_raw / d x, d / d y, d / d z, sigma_raw] of
+ * CodeNeRFModel.forward's density (model.py:174-186) at m = n_rays * n_samples points -- surface normals
+ * are -gradient / |gradient|.  One launch: cn_density_field's 10 weight chunks with both ReLU masks kept
+ * in registers, then the last 10 chunks of the fused backward (layer_xyz2^T, layer_xyz1^T and the
+ * encoding's derivative) with d sigma_raw = 1; 327,680 FLOP per point.  Column 3 is bit for bit
+ * cn_density_field's sigma_raw; columns 0..2 equal, value for value, the d_pts that
+ * cn_radiance_field_masks + cn_field_backward_fused give for d_raw = (0, 0, 0, 1).
+ * packed: the CN_FMT_F32_W16 cn_mlp_pack (fmt), packed_t: the CN_FMT_F32_W16_T one (fmt_t), of the same
+ * parameters, both unchanged; a valid forward / transposed pair in other formats returns
+ * CN_EUNSUPPORTED before any launch.  Exactly one input mode:
+ *   pts (m, 3);
+ *   ro, rd (n_rays, 3) and z (n_rays, n_samples): pts = ro + rd*z as cn_radiance_field forms them; the
+ *     gradient is with respect to that point (nothing flows to ro, rd or z).
+ * code row of sample k = that of ray r = k / n_samples, as in cn_density_field: code_index[r], or row 0
+ * (n_codes == 1), or row r (n_codes == n_rays).  freqs_xyz (10): a HOST array.
+ * grad_sigma: 16-byte aligned, every row written (a non-finite point gives NaN).  Stream-ordered on
+ * `stream`, no workspace, no synchronisation, nothing retained after return: capturable in a graph.
+ * CN_EINVAL before any launch: a NULL packed, packed_t, code_bias, freqs_xyz or grad_sigma; not exactly
+ * one mode (or a partial ro / rd / z); grad_sigma misaligned; a size <= 0; n_codes neither 1 nor n_rays
+ * without a code_index; fmt not a forward format or fmt_t not a transposed one (unknown values, or the
+ * two packs swapped). */
+int cn_density_gradient(const float* packed, const float* packed_t, int fmt, int fmt_t, const float* code_bias,
+                        const int64_t* code_index, int64_t n_codes, const float* pts, const float* ro,
+                        const float* rd, const float* z, int64_t n_rays, int64_t n_samples,
+                        const float* freqs_xyz, float* grad_sigma, cn_stream_t stream);
+
 /* --- Occupancy-grid sample culling (inference) --------------------------
  * A grid is the cube [-bound, bound]^3 cut into g^3 cells, g a multiple of 32 in [32, 512], one bit
  * per cell in g^3 / 32 32-bit words of device memory: cell (ix, iy, iz) has linear index
