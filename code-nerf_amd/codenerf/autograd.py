@@ -249,6 +249,10 @@ class PoseRays(torch.autograd.Function):
     def backward(ctx, g_ro, g_rd, _g_c2w, _g_tgt):
         none = [None] * 8
         sink, ctx.sink = ctx.sink, None
+        if sink is not None and sink.hold is not None:
+            # a field still waits for a partner that never ran (the loss reaches one field, or the other
+            # could not pair): its ray gradients belong to the sums read below, so it runs now
+            _pair_flush(sink.hold)
         if sink is not None and sink.buf is not None:
             # the consumers that added their ray gradients in place (RaySink), plus any that did not
             s_ro, s_rd = sink.buf
@@ -454,13 +458,18 @@ def new_field_pair():
 
 
 def _pair_flush(pair):
-    """End of the backward pass (queued by the waiting field): a field whose partner never ran its
-    backward runs alone.  Its code gradient must still reach the code rows' sink."""
+    """A field whose partner never ran its backward (or cannot pair) runs alone: called by whatever reads
+    the sums it adds into -- PoseRays.backward (the RaySink), CodeGradSink.take() (the code rows), a partner
+    that cannot pair -- so its gradients are complete in whatever order autograd runs those; the callback the
+    waiting field queued for the end of the backward pass then finds nothing left.  Its code gradient must
+    still reach the code rows' sink."""
     if pair.pending is None:
         return
     job, post = pair.pending
     pair.pending = None
     meta, params, z_s, z_t, pg, want_z, act = post
+    if meta.sink is not None and meta.sink.hold is pair:
+        meta.sink.hold = None
     if want_z and (meta.sink is None or meta.sink.rows() is None):
         raise RuntimeError("paired field backward: the partner field never ran and the code rows' gradient "
                            "buffers were already handed out")
@@ -479,17 +488,19 @@ def _pair_flush(pair):
 def _code_grads_pair(first, second):
     """_code_grads of a FieldPair's two fields (first: the one that waited) with their first halves in one
     launch (cn_code_bias_backward_act_multi); their dz queued in that order.  Each item: (meta, params, z_s,
-    z_t, g_code, pg, want_z, act) with act given.  -> (dz_s, dz_t) of the second."""
+    z_t, g_code, pg, want_z, act) with act given.  -> (dz_s, dz_t) of the code rows: what the sinks did not take.
+    (A first field only waits when its sink takes its dz; were it not to, its dz is added, not dropped.)"""
     items = (first, second)
     wss = ops.code_ds_outer_multi([(it[1], it[7], it[4], it[5]) for it in items], first[2], first[3])
-    out = None
+    out = (None, None)
     for (meta, params, z_s, z_t, g_code, pg, want_z, act), ws in zip(items, wss):
-        out = (None, None)
         if not want_z:
             continue
         if meta.sink is not None and meta.sink.defer(params, g_code, ws):
             continue
-        out = ops.code_dz([(params, g_code, ws)], z_s.shape[0])
+        # (both fields read the same code rows: a dz the sink did not take is returned, the two summed)
+        dz = ops.code_dz([(params, g_code, ws)], z_s.shape[0])
+        out = dz if out[0] is None else (out[0] + dz[0], out[1] + dz[1])
     return out
 
 
@@ -609,6 +620,8 @@ class RadianceField(torch.autograd.Function):
                     if pairable:         # the first of the pair waits for the other
                         pair.pending = (job, post)
                         pair.sink, rs.hold = rs, pair
+                        if want_z:
+                            meta.sink.hold = pair     # (take() runs the waiting field before it hands the rows out)
                         torch.autograd.Variable._execution_engine.queue_callback(lambda: _pair_flush(pair))
                         return (None,) * len(needs)
                 elif not pairable:
@@ -617,6 +630,8 @@ class RadianceField(torch.autograd.Function):
                     other_job, other_post = pair.pending
                     pair.pending = None
                     pair.sink.hold, pair.sink = None, None
+                    if other_post[0].sink is not None:
+                        other_post[0].sink.hold = None
                     between, pair.between = pair.between, None
                     r_other, r = ops.field_backward_x3_multi([other_job, job], d_rd_between=between)
                     dz_s, dz_t = _code_grads_pair(other_post[:4] + (r_other["g_code"],) + other_post[4:],
@@ -650,6 +665,8 @@ class RadianceField(torch.autograd.Function):
                     if (slots and act is not None and not any(needs[1:4])
                             and (not want_z or (meta.sink is not None and meta.sink.rows() is not None))):
                         pair.pending = (job, post)
+                        if want_z:
+                            meta.sink.hold = pair     # (take() runs the waiting field before it hands the rows out)
                         for p, g in zip(orig, pg):
                             p.grad = g                  # filled by the shared launch, on the stream
                         torch.autograd.Variable._execution_engine.queue_callback(lambda: _pair_flush(pair))
@@ -657,6 +674,8 @@ class RadianceField(torch.autograd.Function):
                 else:
                     other_job, other_post = pair.pending
                     pair.pending = None
+                    if other_post[0].sink is not None:
+                        other_post[0].sink.hold = None
                     r_other, r = ops.field_backward_train_multi([other_job, job], meta.precision)
                     if act is not None and other_post[6] is not None:
                         dz_s, dz_t = _code_grads_pair(other_post[:4] + (r_other["g_code"],) + other_post[4:],

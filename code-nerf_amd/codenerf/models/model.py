@@ -203,10 +203,11 @@ class CodeGradSink:
     their .grad by _TableRow.backward.  Per model and step this replaces an add of the coarse and fine
     code gradients and one into the table row (nn.Embedding's backward, model.py:102-105)."""
 
-    __slots__ = ("tables", "k", "bufs", "pending")
+    __slots__ = ("tables", "k", "bufs", "pending", "hold")
 
     def __init__(self, tables, k: int):
         self.tables, self.k, self.bufs, self.pending = tables, k, None, []
+        self.hold = None     # an autograd.FieldPair whose waiting field still owes its dz to these rows
 
     def rows(self):
         """-> (shape row, texture row) views (1, code size) of the claimed gradient buffers, or None when a
@@ -240,7 +241,11 @@ class CodeGradSink:
 
     def take(self):
         """-> the claimed buffers or None (after flush()), dropping the sink's references to them
-        (AccumulateGrad then adopts them as .grad without a copy)."""
+        (AccumulateGrad then adopts them as .grad without a copy).  A field backward still waiting for a
+        partner that never ran (autograd.FieldPair) runs first: its dz belongs to these rows."""
+        if self.hold is not None:
+            from ..autograd import _pair_flush
+            _pair_flush(self.hold)
         self.flush()
         b, self.bufs = self.bufs, None
         return b

@@ -1343,8 +1343,9 @@ def field_backward_x3(packed_t: Tensor, masks: Tensor, d_raw: Tensor, n_rays: in
     ``acc``: a zeroed buffer of field_backward_x3_acc_floats(...) floats for the accumulated outputs
     (field_prepare's), else one is allocated and filled.  ``ray_into`` ((R, 3) d ro, d rd device tensors,
     with want_ro and want_rd): the ray gradients are ADDED into those instead.  ``deterministic`` (default):
-    with one code row and S % 32 (bf16x3) / % 16 (f32) == 0, cn_field_backward_fused_ws's form without
-    float atomics, so repeated backwards give the same bits (False: the float-atomic kernel)."""
+    with one code row and, for bf16x3, S % 32 == 0, cn_field_backward_fused_ws's form without float atomics,
+    so repeated backwards give the same bits (False: the float-atomic kernel).  fp32 takes it at every S:
+    with S % 16 == 0 a wave's ray sums are one partial row, else each sample's are."""
     fmt_t = _lib.CN_FMT_BF16X3_T if precision == "bf16x3" else _lib.CN_FMT_F32_W16_T
     lib = _lib_ready()
     m = n_rays * n_samples
@@ -1370,10 +1371,10 @@ def field_backward_x3(packed_t: Tensor, masks: Tensor, d_raw: Tensor, n_rays: in
     d_pts = torch.empty(n_rays, n_samples, 3, device=dev, dtype=torch.float32) if want_pts else None
     if m == 0:      # no samples: zero sums (the C ABI refuses n_rays == 0)
         return {"g_code": g_code, "d_pts": d_pts, "d_ro": d_ro, "d_rd": d_rd}
-    # one code row, every wave inside one ray: the deterministic form (no float atomics; its partials in a
-    # workspace, summed in a fixed order by two short launches), else the float-atomic kernel
+    # one code row (3xbf16: and every wave inside one ray): the deterministic form (no float atomics; its
+    # partials in a workspace, summed in a fixed order by two short launches), else the float-atomic kernel
     ws = None
-    if deterministic and n_codes == 1 and n_samples % (32 if precision == "bf16x3" else 16) == 0:
+    if deterministic and n_codes == 1 and (precision != "bf16x3" or n_samples % 32 == 0):
         ws = torch.empty(int(lib.cn_field_backward_fused_workspace_floats(fmt_t, n_rays, n_samples)), device=dev,
                          dtype=torch.float32)
     check(lib.cn_field_backward_fused_ws(fmt_t, ptr(packed_t), ptr(masks), ptr(d_raw), ptr(pts), ptr(ro), ptr(rd),

@@ -41,6 +41,9 @@ class AdamW(torch.optim.Optimizer):
     # whose collective stream waits for the enqueued work without a host wait (gloo stages device tensors
     # through the host; the two-rank gloo tests add it to check the bucketed sums)
     bucket_backends = ("nccl",)
+    # the first bucket: the leading parameter groups (the two MLPs of train.prepare_optimizer; fewer groups:
+    # all of them).  A constant, like the backend the same on every rank, so every rank splits alike
+    bucket_groups = 2
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, amsgrad: bool = False, *, maximize: bool = False,
@@ -169,6 +172,7 @@ class AdamW(torch.optim.Optimizer):
         ``p._cn_grad_slot``: a fused backward that finds ``p.grad is None`` accumulates straight
         into that (zeroed) slice and returns it, so autograd installs it as ``p.grad`` with no
         per-parameter fill or copy (autograd.RadianceField)."""
+        self._pending_bucket = None       # (a bucket begun in a step that never reached allreduce_grads)
         self._flat["grad"].zero_()
         for p in self._offs:
             p._cn_grad_slot = self._view("grad", p)
@@ -275,19 +279,28 @@ class AdamW(torch.optim.Optimizer):
         self._adopt_state()
 
     # ---- data parallel ------------------------------------------------
+    def _bucket_split(self) -> int:
+        """Where the flat gradient splits into the two buckets of a bucket-enabled backend: the end of the
+        first ``bucket_groups`` parameter groups.  From the layout alone, so the same on every rank."""
+        return self._starts[min(self.bucket_groups, len(self.param_groups))]
+
     def allreduce_begin(self, n_groups: int, group=None) -> bool:
-        """Start the all-reduce of the first ``n_groups`` parameter groups' gradients now, asynchronously
-        (the first bucket of DDP's overlap, util.py:139-142): called from inside the backward once those
-        gradients are final -- train_minibatch hands it to the render's FieldPair, which calls it right
-        after both fields' weight gradients are enqueued -- so the collective runs while the rest of the
-        backward (the code tables' dz, the pose / ray tail) does; allreduce_grads() then reduces the rest
-        and waits for both.  On RCCL the collective's stream waits for the work enqueued so far and runs
-        beside what follows.  Only when every parameter of those groups holds its gradient (else nothing
-        starts and allreduce_grads() reduces everything at once).  -> whether it started."""
+        """Start the all-reduce of the first ``n_groups`` (== ``bucket_groups``) parameter groups' gradients
+        now, asynchronously (the first bucket of DDP's overlap, util.py:139-142): called from inside the
+        backward once those gradients are final -- train_minibatch hands it to the render's FieldPair, which
+        calls it right after both fields' weight gradients are enqueued -- so the collective runs while the
+        rest of the backward (the code tables' dz, the pose / ray tail) does; allreduce_grads() then reduces
+        the rest and waits for both.  On RCCL the collective's stream waits for the work enqueued so far and
+        runs beside what follows.  Only when every parameter of those groups holds its gradient in its flat
+        slice; else nothing starts here and allreduce_grads() issues this same collective itself, so a rank
+        that started and one that did not still issue the same two.  -> whether it started."""
         if not (dist.is_available() and dist.is_initialized()) or getattr(self, "_pending_bucket", None):
             return False
         if dist.get_backend(group) not in self.bucket_backends:
             return False
+        if min(n_groups, len(self.param_groups)) != min(self.bucket_groups, len(self.param_groups)):
+            raise ValueError(f"allreduce_begin({n_groups}): the first bucket is bucket_groups = "
+                             f"{self.bucket_groups} parameter groups on every rank")
         params = [p for g in self.param_groups[:n_groups] for p in g["params"]]
         if any(p.grad is None for p in params):
             return False
@@ -296,25 +309,33 @@ class AdamW(torch.optim.Optimizer):
                 view = self._view("grad", p)
                 if p.grad.data_ptr() != view.data_ptr():
                     return False
-        split = self._starts[n_groups]
+        split = self._bucket_split()
         work = dist.all_reduce(self._grad_ext[:split], op=dist.ReduceOp.SUM, group=group, async_op=True)
         self._pending_bucket = (split, work, group)
         return True
 
     def allreduce_grads(self, group=None, average: bool = True) -> None:
-        """Average the gradients over the process group (the reference's DDP, util.py:139-142):
-        ONE all-reduce (SUM, then a division by the world size -- the same arithmetic on RCCL and
-        gloo) of the flat gradient buffer with a per-parameter has-grad flag appended to it
-        (``average=False``: the plain sum, for losses the ranks already weighted -- the ray-sharded
-        eval step, codenerf.evaluate.sharded_eval_step).  A
-        gradient missing on this rank counts as zero; a parameter without a gradient on every rank
-        keeps ``grad = None``.
+        """Average the gradients over the process group (the reference's DDP, util.py:139-142): a SUM
+        all-reduce, then a division by the world size -- the same arithmetic on RCCL and gloo -- of the
+        flat gradient buffer with a per-parameter has-grad flag appended to it (``average=False``: the
+        plain sum, for losses the ranks already weighted -- the ray-sharded eval step,
+        codenerf.evaluate.sharded_eval_step).  A gradient missing on this rank counts as zero; a parameter
+        without a gradient on every rank keeps ``grad = None``.
+
+        The collectives a rank issues depend on the backend and the buffer layout alone, never on which
+        gradients it holds or on whether allreduce_begin started: on a bucket-enabled backend
+        (``bucket_backends``) always two, the first ``bucket_groups`` parameter groups' part and then the
+        rest with the flags -- the first one issued here, after zeroing the missing gradients, unless
+        allreduce_begin already did; on any other backend (gloo by default) always one over the whole
+        buffer.
 
         No host synchronisation when every parameter holds a gradient here (every training step
         of the reference: each chunk runs both models and both code tables): the flags are a
         cached device tensor per has-grad pattern, copied into the buffer's tail, and only a rank
         that lacks some gradient reads the reduced flags back (to know whether another rank has
-        it).  Every rank always issues the same single collective, whatever its pattern."""
+        it)."""
+        # whatever happens below, no bucket of this step is left for the next one to mistake for its own
+        pending, self._pending_bucket = getattr(self, "_pending_bucket", None), None
         if not (dist.is_available() and dist.is_initialized()):
             return
         world = dist.get_world_size(group)
@@ -331,14 +352,21 @@ class AdamW(torch.optim.Optimizer):
         ext[n:n + len(params)].copy_(flags)
         for p in missing:
             self._view("grad", p).zero_()
-        pending, self._pending_bucket = getattr(self, "_pending_bucket", None), None
-        if pending is not None:
-            # the first bucket went out during the backward (allreduce_begin): the rest now, then both done
-            split, work, group0 = pending
-            assert group0 is group, "allreduce_begin / allreduce_grads on different groups"
+        if dist.get_backend(group) in self.bucket_backends:
+            split = self._bucket_split()
+            work = None
+            if pending is not None:
+                # the first bucket went out during the backward (allreduce_begin): the rest now, then both done
+                split0, work, group0 = pending
+                assert group0 is group, "allreduce_begin / allreduce_grads on different groups"
+                assert split0 == split, "allreduce_begin's bucket is not the layout's"
+            else:
+                dist.all_reduce(ext[:split], op=dist.ReduceOp.SUM, group=group)
             dist.all_reduce(ext[split:], op=dist.ReduceOp.SUM, group=group)
-            work.wait()
+            if work is not None:
+                work.wait()
         else:
+            assert pending is None, "a gradient bucket was begun on a backend without buckets"
             dist.all_reduce(ext, op=dist.ReduceOp.SUM, group=group)
         if average:
             ext.div_(world)

@@ -3255,8 +3255,9 @@ static grad::GcFinal gc_final(const float* rows, int64_t n_rows, float* g_code) 
   return grad::GcFinal{rows, n_rows, g_code, blocks};
 }
 
-static int64_t fused_ws_layout(int fmt_t, int64_t m, int64_t* ray_off, int64_t* q1_off, int64_t* rows_off) {
-  const int64_t ws = fmt_t == CN_FMT_BF16X3_T ? 32 : 16;
+// ``ws``: the samples per ray row -- a wave's 16 (fp32) / 32 (3xbf16) with whole waves per ray, else 1
+// (fused_ray_row_samples).
+static int64_t fused_ws_layout(int64_t ws, int64_t m, int64_t* ray_off, int64_t* q1_off, int64_t* rows_off) {
   // the launch's grid is at most one workgroup per 128-sample tile and kMaxBwdBlocks
   const int64_t blocks = std::min<int64_t>(ceil_div(m, 128), mlp::kMaxBwdBlocks);
   const int64_t gc = blocks * mlp::kMaxBwdWaves * mlp::kCbStride;
@@ -3268,9 +3269,18 @@ static int64_t fused_ws_layout(int fmt_t, int64_t m, int64_t* ray_off, int64_t* 
   return gc + rows + rp + 3 * m;
 }
 
+// The samples one ray_part row sums: a wave's when every wave lies inside one ray; else, fp32, the row is
+// one sample's (the 3xbf16 kernel has no such form: 0, and that shape runs the float-atomic kernel).
+static int fused_ray_row_samples(int fmt_t, int64_t n_samples) {
+  const int wave_samples = fmt_t == CN_FMT_BF16X3_T ? 32 : 16;
+  if (n_samples % wave_samples == 0) return wave_samples;
+  return fmt_t == CN_FMT_BF16X3_T ? 0 : 1;
+}
+
 extern "C" int64_t cn_field_backward_fused_workspace_floats(int fmt_t, int64_t n_rays, int64_t n_samples) {
   if (!(fmt_t == CN_FMT_BF16X3_T || fmt_t == CN_FMT_F32_W16_T) || n_rays <= 0 || n_samples <= 0) return -1;
-  return fused_ws_layout(fmt_t, n_rays * n_samples, nullptr, nullptr, nullptr);
+  const int row = fused_ray_row_samples(fmt_t, n_samples);
+  return fused_ws_layout(row ? row : 32, n_rays * n_samples, nullptr, nullptr, nullptr);
 }
 
 extern "C" int cn_field_backward_fused_ws(int fmt_t, const float* packed_t, const uint32_t* masks,
@@ -3285,13 +3295,13 @@ extern "C" int cn_field_backward_fused_ws(int fmt_t, const float* packed_t, cons
   hipStream_t st = as_stream(stream);
   const int mode = pts ? mlp::kFromPts : mlp::kFromRayZ;
   const bool x3 = fmt_t == CN_FMT_BF16X3_T;
-  const int wave_samples = x3 ? 32 : 16;
-  // the deterministic form needs one code row (g_code: one row per workgroup) and every wave inside
-  // one ray (the ray rows); otherwise the float-atomic kernel
-  const bool det = workspace && n_codes == 1 && n_samples % wave_samples == 0;
+  // the deterministic form needs one code row (g_code: one row per workgroup) and ray rows: a wave's with
+  // every wave inside one ray, else (fp32) a sample's; otherwise the float-atomic kernel
+  const int wave_samples = fused_ray_row_samples(fmt_t, n_samples);
+  const bool det = workspace && n_codes == 1 && wave_samples > 0;
   int64_t ray_off = 0, q1_off = 0, rows_off = 0;
   if (det) {
-    fused_ws_layout(fmt_t, a.m, &ray_off, &q1_off, &rows_off);
+    fused_ws_layout(wave_samples, a.m, &ray_off, &q1_off, &rows_off);
     a.gc_part = workspace;
     a.ray_part = mode == mlp::kFromRayZ && (d_ro || d_rd) ? workspace + ray_off : nullptr;
     a.q1_part = d_rd ? workspace + q1_off : nullptr;
@@ -3347,7 +3357,7 @@ extern "C" int cn_field_backward_fused_multi(int fmt_t, const cn_field_fused_bwd
                                       f.n_samples, f.chunk_rows, f.code_index, f.n_codes, f.freqs_xyz, f.freqs_dir,
                                       f.g_code, f.d_pts, f.d_ro, f.d_rd, a[k]));
       int64_t ray_off = 0, q1_off = 0, rows_off = 0;
-      fused_ws_layout(fmt_t, a[k].m, &ray_off, &q1_off, &rows_off);
+      fused_ws_layout(16, a[k].m, &ray_off, &q1_off, &rows_off);
       a[k].gc_part = f.workspace;
       a[k].ray_part = (f.d_ro || f.d_rd) ? f.workspace + ray_off : nullptr;
       a[k].q1_part = f.d_rd ? f.workspace + q1_off : nullptr;

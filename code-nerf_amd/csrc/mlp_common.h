@@ -50,7 +50,8 @@ struct FieldArgs {
   // one ray): no float atomics -- partials a fixed-order reduction adds up afterwards
   float* gc_part;        // (blocks x waves, kCbStride): each wave's g_code row
   float* gc_rows;        // fp32: set -> each workgroup's wave rows summed in wave order, one row per workgroup
-  float* ray_part;       // (m / wave samples, 6): each wave's d ro, d rd of its ray (the points' part)
+  float* ray_part;       // (m / wave samples, 6): each wave's d ro, d rd of its ray (the points' part);
+                         // fp32 with S % 16 != 0: (m, 6), each sample's
   float* q1_part;        // (m, 3): each sample's d rd of its Q1 view-direction ray
   int64_t n_blocks;      // set by the backward launchers: the grid they launched
   // folded fp32 inference forward (CN_FMT_F32_W16_FOLD): (n_codes, 256) c_v1 rows of cn_fold_bias

@@ -1953,10 +1953,11 @@ __device__ __forceinline__ void bwd_tile(State& s, const FieldArgs& a, float4* l
     if (valid && s.g == 0 && (!one_ray || s.lane == 0)) {
       const int64_t ray = rc / S;
       if constexpr (DET) {
-        // deterministic form (one ray per wave, host-checked): the wave's sums as its row of ray_part
-        // (lane 0's rc is the wave's first sample, a multiple of 16)
+        // deterministic form: with one ray per wave the wave's sums as its row of ray_part (lane 0's rc is
+        // the wave's first sample, a multiple of 16); else each sample's own as its row (the host sized
+        // ray_part for that and sums a ray's S rows)
         if (a.ray_part) {
-          float* p = a.ray_part + (rc >> 4) * 6;
+          float* p = a.ray_part + (one_ray ? (rc >> 4) : rc) * 6;
           for (int d = 0; d < 3; ++d) {
             p[d] = gro[d];
             p[3 + d] = grd[d];

@@ -641,8 +641,9 @@ int cn_field_backward_fused(int fmt_t, const float* packed_t, const uint32_t* ma
                             const float* freqs_xyz, const float* freqs_dir, float* g_code, float* d_pts,
                             float* d_ro, float* d_rd, cn_stream_t stream);
 /* The same backward without float atomics (eval.py:145-160's backward, bit-reproducible): with
- * n_codes == 1 and n_samples % 32 (bf16x3) / % 16 (fp32) == 0 the kernel writes per-workgroup g_code
- * rows and per-wave / per-sample ray-gradient terms into workspace
+ * n_codes == 1 and, for bf16x3, n_samples % 32 == 0 the kernel writes per-workgroup g_code
+ * rows and per-wave / per-sample ray-gradient terms (fp32 with n_samples % 16 != 0: the points' terms per
+ * sample too, 6 floats each instead of 6 per wave of 16) into workspace
  * (cn_field_backward_fused_workspace_floats(fmt_t, n_rays, n_samples) floats, 16-B aligned; contents on
  * entry are ignored: a wave or workgroup without rows stores its zero row or is skipped by the sums),
  * and two short launches add them into g_code, d_ro and d_rd in a fixed order (g_code / d_ro / d_rd are

@@ -125,6 +125,14 @@ def test_deterministic_eval_backward_workspace(lib_path):
             blocks = min((m + 127) // 128, 512)
             want = blocks * 8 * 520 + blocks * 520 + up4((m + ws - 1) // ws * 6) + 3 * m
             assert lib.cn_field_backward_fused_workspace_floats(fmt_t, n_rays, s) == want, (fmt_t, n_rays, s)
+        # samples that do not fill whole waves: fp32 keeps 6 floats per SAMPLE (its deterministic form at
+        # every sample count); 3xbf16 has no such form there and sizes as before
+        for n_rays, s in ((100, 56), (100, 24), (7, 1)):
+            m = n_rays * s
+            blocks = min((m + 127) // 128, 512)
+            rows = m if ws == 16 else (m + ws - 1) // ws
+            want = blocks * 8 * 520 + blocks * 520 + up4(rows * 6) + 3 * m
+            assert lib.cn_field_backward_fused_workspace_floats(fmt_t, n_rays, s) == want, (fmt_t, n_rays, s)
         assert lib.cn_field_backward_fused_workspace_floats(fmt_t, 0, 64) == -1
     assert lib.cn_field_backward_fused_workspace_floats(_lib.CN_FMT_F32_W16, 16, 64) == -1   # not a transposed pack
     args = [_lib.CN_FMT_F32_W16_T] + [None] * 7 + [1, 64, 1, None, 1, None, None, None, None, None, None, None, None]

@@ -145,8 +145,8 @@ def test_ddp_drop_in_rccl(dev, rccl_world1):
 
 def test_train_minibatch_no_host_sync_rccl(dev, rccl_world1):
     """The data-parallel chunk step (train.py:96-114 + util.py:139-142's gradient average) over RCCL
-    runs with no host synchronisation: AdamW.allreduce_grads issues ONE all-reduce of the flat
-    gradient with its has-grad flags appended (a cached device tensor) and reads nothing back when
+    runs with no host synchronisation: AdamW.allreduce_grads reduces the flat gradient with its has-grad
+    flags appended (a cached device tensor; on RCCL in its two buckets) and reads nothing back when
     every parameter holds a gradient; torch's sync debug mode "error" raises on any sync."""
     import numpy as np
     from codenerf import train as T

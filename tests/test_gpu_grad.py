@@ -749,7 +749,7 @@ def test_field_backward_train_nogeo_bitwise(dev, precision, mode, r, s, n_codes)
                                             ("pts", 37, 32, 37)])
 def test_fused_backward_deterministic(dev, precision, mode, r, s, chunk):
     """The eval backward without float atomics (cn_field_backward_fused_ws, the default of
-    ops.field_backward_x3 for one code row and whole waves per ray): per-wave g_code rows, per-wave
+    ops.field_backward_x3 for one code row and, 3xbf16, whole waves per ray): per-wave g_code rows, per-wave
     ray rows and per-sample Q1 terms summed in a fixed order.  Two runs give the same bits; the
     float-atomic kernel agrees to fp32 reassociation; d ro / d rd are ADDED into given tensors."""
     from codenerf import ops, synthetic
@@ -785,6 +785,16 @@ def test_fused_backward_deterministic(dev, precision, mode, r, s, chunk):
         into = (base[0].clone(), base[1].clone())
         run(True, ray_into=into)
         assert torch.equal(into[0], base[0] + a["d_ro"]) and torch.equal(into[1], base[1] + a["d_rd"])
+
+
+@pytest.mark.parametrize("r,s,chunk", [(100, 56, 100), (100, 24, 100), (53, 7, 20), (300, 40, 128)])
+def test_fused_backward_deterministic_part_waves(dev, r, s, chunk):
+    """The fp32 eval backward without float atomics at sample counts that do not fill whole waves per ray
+    (S % 16 != 0: a wave's 16 samples straddle rays, so each sample's d ro / d rd terms are their own
+    partial row and a ray's S rows are summed in a fixed order): test_fused_backward_deterministic's
+    checks at those shapes -- 56 and 24 are the eval step's 32 + 24 fine and 24 + 40 coarse fields; 7 and a
+    short last Q1 chunk; more rays than one tile holds."""
+    test_fused_backward_deterministic(dev, "f32", "rayz", r, s, chunk)
 
 
 @pytest.mark.parametrize("n_codes,want_grads", [(1, True), (5, True), (5, False)])

@@ -215,12 +215,14 @@ C5_CHAIRS_RTOL = 1e-4
 C5_CHAIRS_LOSS = 1e-6
 
 
-def test_eval_c5_chairs_fused_at_size(dev):
+def test_eval_c5_chairs_fused_at_size(dev, monkeypatch):
     """eval.py:141-168 at srn-chairs-code.yml's shape (make_golden.py gen_c5_chairs: num_random_rays 4096
     of a 128x128 view, 32 + 128 perturbed samples -- a 160-sample fine pass -- near 1.25 / far 2.75, the
-    reference's draws re-made from its seed) through eval_step_loss's fused path, fp32: rendered rgb,
-    loss and d(theta, phi, rho, z_s, z_t) vs the reference; a second run bit for bit."""
-    from codenerf import synthetic
+    reference's draws re-made from its seed) through eval_step_loss's fused path, fp32: the rendered
+    rgb_coarse and rgb_fine the step hands to its loss (evaluate.nerf_loss's first two arguments) against
+    the fixture's, every pixel and channel at 1e-4; loss and d(theta, phi, rho, z_s, z_t) vs the reference;
+    a second run bit for bit, the two images included."""
+    from codenerf import evaluate as E, synthetic
     from codenerf.evaluate import eval_step_loss
     from codenerf.nerf import PointSampler, RaySampler
     from conftest import margin
@@ -232,6 +234,12 @@ def test_eval_c5_chairs_fused_at_size(dev):
     rs = RaySampler(128, 128, synthetic.srn_intrinsics(128), sample_size=4096, device=dev, datatype=torch.float32)
     ps = PointSampler(32, 128, 1.25, 2.75, "lindepth", True, torch.float32, dev)
     models = _eval_models(dev)
+    seen, real_loss = {}, E.nerf_loss
+
+    def spy_loss(rgb_c, rgb_f, *a, **k):
+        seen["rgb_coarse"], seen["rgb_fine"] = rgb_c.detach().clone(), rgb_f.detach().clone()
+        return real_loss(rgb_c, rgb_f, *a, **k)
+    monkeypatch.setattr(E, "nerf_loss", spy_loss)
     runs = []
     for rep in range(2):
         lv = [g[k].clone().requires_grad_(True) for k in ("theta", "phi", "rho", "z_s", "z_t")]
@@ -239,11 +247,14 @@ def test_eval_c5_chairs_fused_at_size(dev):
         loss, logs = eval_step_loss(*lv, g["target"], (rs, ps), embedders(dev), models, 1e-5, t_rand=t_rand, u=u)
         loss.backward()
         torch.cuda.synchronize()
-        runs.append((loss.item(), [t.grad.clone() for t in lv]))
+        runs.append((loss.item(), [t.grad.clone() for t in lv] + [seen["rgb_coarse"], seen["rgb_fine"]]))
     assert runs[0][0] == runs[1][0]
     for a, b in zip(runs[0][1], runs[1][1]):
         assert torch.equal(a, b)
     tag = "eval_c5_chairs[f32]"
+    for key in ("rgb_coarse", "rgb_fine"):
+        assert seen[key].shape == g[key].shape and seen[key].dtype == torch.float32, key
+        margin(tag, key, (seen[key].double() - g[key].double()).abs().max().item(), 1e-4)
     margin(tag, "loss", abs(runs[0][0] - g["loss"].item()), C5_CHAIRS_LOSS)
     for name, t in zip(("theta", "phi", "rho", "z_s", "z_t"), runs[0][1]):
         ref = g["g_" + name]

@@ -498,6 +498,29 @@ def _proj(r, t):
     return (r.double() * t.detach().double().cpu()[None]).reshape(r.shape[0], -1).sum(1)
 
 
+def spy_step_images(monkeypatch):
+    """The images train_minibatch hands to its loss (train.render_loss_autograd's first two arguments),
+    kept as detached copies -> {"rgb_coarse", "rgb_fine"}, filled by the step."""
+    from codenerf import train as T
+    seen = {}
+    real = T.render_loss_autograd
+
+    def spy(rgb_c, rgb_f, *a, **k):
+        seen["rgb_coarse"], seen["rgb_fine"] = rgb_c.detach().clone(), rgb_f.detach().clone()
+        return real(rgb_c, rgb_f, *a, **k)
+    monkeypatch.setattr(T, "render_loss_autograd", spy)
+    return seen
+
+
+def check_step_pixels(tag, seen, g):
+    """The step's own rgb_coarse and rgb_fine against the reference's (the fixture's), every pixel and
+    channel, at the project's fp32 parity target |d| <= 1e-4."""
+    from conftest import margin
+    for key in ("rgb_coarse", "rgb_fine"):
+        assert seen[key].shape == g[key].shape and seen[key].dtype == torch.float32, key
+        margin(tag, key, (seen[key].double() - g[key].double()).abs().max().item(), 1e-4)
+
+
 _C3_RESULTS = {}
 C3_OBJECTS = 2458
 C3_IDS = [17, 1234]
@@ -534,10 +557,11 @@ def _c3_setup(dev, precision):
 
 @pytest.mark.parametrize("host_ids", [False, True])
 @pytest.mark.parametrize("precision", ["f32", "bf16x3"])
-def test_train_c3_chunk_at_size(dev, precision, host_ids):
+def test_train_c3_chunk_at_size(dev, monkeypatch, precision, host_ids):
     """C3 at size vs the reference's own chunk step (train_c3.npz, make_golden.py gen_c3train:
     train.py:96-114 on one 4096-ray chunk of two objects of a 2458-object table, 64 + 64 perturbed
-    samples with the reference's draws, AdamW + LambdaLR), element-wise: the losses; nerf_fine's
+    samples with the reference's draws, AdamW + LambdaLR), element-wise: the losses; for fp32 the
+    rendered rgb_coarse and rgb_fine the step hands to its loss, every pixel at 1e-4; nerf_fine's
     gradients and post-step values in full; for nerf_coarse five tensors in full and 16 seeded
     projections of EVERY tensor's gradient and post-step change; the two touched code rows'
     gradients and values, every untouched row only decayed.  ``host_ids``: the chunk's object ids
@@ -553,9 +577,12 @@ def test_train_c3_chunk_at_size(dev, precision, host_ids):
     ids_t = g["ids"].long()
     if host_ids:
         ids_t._cn_host_ids = g["ids"].long().cpu().numpy()
+    seen = spy_step_images(monkeypatch)
     logs = T.train_minibatch(models, opt, sched, ps, embedders(dev), g["ro"], g["rd"], ids_t, g["target"],
                              1e-5, uniforms=(t_rand.to(dev), u.to(dev)))
     torch.cuda.synchronize()
+    if precision == "f32":
+        check_step_pixels(tag, seen, g)
     got_l = {"lc": logs["nerf_loss_coarse"], "lf": logs["nerf_loss_fine"], "reg": logs["embedding_loss"],
              "loss": logs["total_loss"]}
     for k, v in got_l.items():
@@ -629,15 +656,17 @@ SHAPE_PROJ_RTOL = {"train_cars_code": 1.9e-3, "train_3080": 1.4e-3}
 
 
 @pytest.mark.parametrize("name", ["train_cars_code", "train_3080"])
-def test_train_shape_chunk_at_size(dev, name):
+def test_train_shape_chunk_at_size(dev, monkeypatch, name):
     """The reference's own runnable training shapes, one chunk step each vs the reference
     (make_golden.py gen_train_shape): srn-cars-code.yml (Nc 32 / Nf 128: a 160-sample fine pass,
     chunk 4096) and srn-cars-code-3080.yml (64 / 128: 192 fine samples, chunk 1024 -- the first chunk
     of a 4096-ray draw), perturbed samples with the reference's draws, one object per chunk (the
     deterministic path every runnable config takes), AdamW + LambdaLR.  fp32 (the reference's
-    precision) through train_minibatch: losses, rendered rgb, five gradients in full, 16 projections of
-    every gradient and post-step change, the touched code row (gradient and post-step), every other row
-    only decayed.  Run twice: the step is bit-reproducible."""
+    precision) through train_minibatch: losses; the rendered rgb_coarse and rgb_fine the step hands to its
+    loss (train.render_loss_autograd's first two arguments) against the fixture's, every pixel and channel
+    at 1e-4; five gradients in full, 16 projections of every gradient and post-step change, the touched
+    code row (gradient and post-step), every other row only decayed.  Run twice: the step (its two images
+    included) is bit-reproducible."""
     from codenerf import synthetic, train as T
     from codenerf.models import CodeNeRFModel, ShapeTextureEmbedding
     from codenerf.nerf import PointSampler
@@ -650,6 +679,7 @@ def test_train_shape_chunk_at_size(dev, name):
     t_rand, u = torch.rand(chunk, nc), torch.rand(chunk, nf)
     assert torch.equal(t_rand[:4].to(dev), g["t_rand_head"]) and torch.equal(u[:4].to(dev), g["u_head"])
     runs = []
+    seen = spy_step_images(monkeypatch)
     for rep in range(2):
         emb_t = ShapeTextureEmbedding(C3_OBJECTS, 256, 256)
         with torch.no_grad():
@@ -671,10 +701,12 @@ def test_train_shape_chunk_at_size(dev, name):
         torch.cuda.synchronize()
         named = {f"{k}.{n}": p for k, m in models.items() for n, p in m.named_parameters()}
         runs.append({k: (p.grad.detach().clone(), p.detach().clone()) for k, p in named.items()})
+        runs[-1].update({k: (v, v) for k, v in seen.items()})
     for k in runs[0]:
         assert torch.equal(runs[0][k][0], runs[1][k][0]) and torch.equal(runs[0][k][1], runs[1][k][1]), \
             ("not bit-reproducible", k)
     tag = f"{name}[f32]"
+    check_step_pixels(tag, seen, g)
     for k, key in (("lc", "nerf_loss_coarse"), ("lf", "nerf_loss_fine"), ("reg", "embedding_loss"),
                    ("loss", "total_loss")):
         margin(tag, "loss " + k, abs(float(logs[key]) - g[k].item()), 1e-5 * max(1.0, abs(g[k].item())))

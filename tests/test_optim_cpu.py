@@ -170,3 +170,86 @@ def test_allreduce_and_broadcast_gloo(world, tmp_path):
     assert np.array_equal(f0["params"], ref10) and np.array_equal(f1["params"], ref10)   # broadcast from rank 0
     for f in (f0, f1):
         assert np.all(f["g0"] == 1.0) and np.all(f["g1"] == 0.5) and np.all(f["g2"] == 1.5) and bool(f["none4"])
+
+
+BUCKET_CASES = ("rank1_never_begins", "rank1_begin_refused", "both_begin")
+
+
+def _int_grads(ps, rank, step):
+    """Distinct small integers per rank, step and element: every sum and its half are exact in fp32."""
+    out, base = [], 0
+    for p in ps:
+        k = p.numel()
+        out.append(((torch.arange(k, dtype=torch.float32) + base) % 251 + 1000.0 * rank + 3.0 * step + 1.0)
+                   .view_as(p))
+        base += k
+    return out
+
+
+def _bucket_worker(rank, world, rdv, out, case):
+    import datetime
+    import torch.distributed as dist
+    dist.init_process_group("gloo", init_method=rdv, rank=rank, world_size=world,
+                            timeout=datetime.timedelta(seconds=30))
+    try:
+        res = {}
+        for tag in ("plain", "bucket"):
+            ps = _params(seed=0)
+            opt = _opt(ps)
+            if tag == "bucket":
+                opt.bucket_backends = ("gloo",)
+            for step in range(2):
+                opt.zero_grad(set_to_none=False)           # the gradients are their flat views
+                with torch.no_grad():
+                    for p, g in zip(ps, _int_grads(ps, rank, step)):
+                        p.grad.copy_(g)
+                if rank == 1 and case == "rank1_begin_refused":
+                    ps[1].grad = None
+                began = None
+                if tag == "bucket" and not (rank == 1 and case == "rank1_never_begins"):
+                    began = opt.allreduce_begin(2)
+                    assert began == (not (rank == 1 and case == "rank1_begin_refused")), began
+                    assert (getattr(opt, "_pending_bucket", None) is not None) == began
+                opt.allreduce_grads()
+                assert getattr(opt, "_pending_bucket", None) is None
+                assert all(p.grad is not None for p in ps)
+                res[f"{tag}{step}"] = torch.cat([p.grad.reshape(-1) for p in ps]).numpy()
+        np.savez(out.format(rank), **res)
+    finally:
+        dist.destroy_process_group()
+
+
+def _spawn_joined(fn, args, nprocs, limit=120.0):
+    """start_processes with a join deadline: ranks that wait for each other forever fail the test."""
+    import time
+    ctx = mp.start_processes(fn, args=args, nprocs=nprocs, join=False, start_method="spawn")
+    deadline = time.monotonic() + limit
+    try:
+        while not ctx.join(timeout=5.0):
+            assert time.monotonic() < deadline, "the ranks did not finish: mismatched collectives"
+    finally:
+        for p in ctx.processes:
+            if p.is_alive():
+                p.kill()
+            p.join()
+
+
+@pytest.mark.parametrize("case", BUCKET_CASES)
+def test_bucketed_allreduce_ranks_disagree(case, tmp_path):
+    """On a bucket-enabled backend the collectives a rank issues do not depend on its own state: a rank
+    whose allreduce_begin started the first bucket, one that never called it and one whose call was refused
+    (a group-0 gradient missing) all reduce ext[:split] and ext[split:], so allreduce_grads returns on
+    both and leaves the gradients of two ranks that never began a bucket (one all-reduce), bit for bit --
+    integer gradients, every sum exact -- with no bucket pending, over two steps."""
+    out = str(tmp_path / "r{}.npz")
+    _spawn_joined(_bucket_worker, (2, rendezvous(), out, case), 2)
+    res = [np.load(out.format(r)) for r in range(2)]
+    ps = _params(seed=0)
+    for step in range(2):
+        g = [_int_grads(ps, r, step) for r in range(2)]
+        if case == "rank1_begin_refused":
+            g[1][1] = torch.zeros_like(g[1][1])            # missing on rank 1: counts as zero
+        want = torch.cat([((a + b) / 2).reshape(-1) for a, b in zip(*g)]).numpy()
+        for r in res:
+            assert np.array_equal(r[f"plain{step}"], want), (case, step)
+            assert np.array_equal(r[f"bucket{step}"], r[f"plain{step}"]), (case, step)
