@@ -36,8 +36,80 @@ def _aligned16(t: Tensor) -> Tensor:
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
+def _opt(t: Optional[Tensor], name: str) -> Optional[Tensor]:
+    return None if t is None else _cuda(t, name)
+
+
 def _lib_ready():
     return _lib.load()
+
+
+# ------------------------------------------------------------------ a field call's inputs
+# The one place the field wrappers get their input checks from (field_api.hip's field_args is its C side):
+# a new wrapper calls one of the two helpers below and adds what is its own.
+
+
+def _freqs(freqs: Sequence[float], count: int, name: str):
+    """The host float array the C side reads ``count`` floats from."""
+    assert freqs is not None and len(freqs) == count, \
+        f"the field kernel implements L_xyz=10, L_dir=4: {name} must have {count} entries"
+    return _lib.host_floats(freqs)
+
+
+def _code_rows(code_index: Optional[Tensor], n_codes: Optional[int], n: int) -> Optional[Tensor]:
+    """The checked ``code_index`` (n,) int64, or without one the rule n_codes in (1, n) (n_codes None: no codes)."""
+    if code_index is not None:
+        code_index = _cuda(code_index, "code_index", torch.int64)
+        assert code_index.shape == (n,), "code_index must be (num_rays,)"
+    elif n_codes is not None:
+        assert n_codes in (1, n), "codes must be one row or one row per ray"
+    return code_index
+
+
+def _ray_inputs(rd: Tensor, n_samples: int, freqs_xyz: Sequence[float], freqs_dir: Sequence[float],
+                pts: Optional[Tensor], ro: Optional[Tensor], z: Optional[Tensor], code_index: Optional[Tensor],
+                n_codes: Optional[int], n_rays: Optional[int] = None):
+    """The ray form of a field call, checked: rd (R, 3) [R = n_rays where the wrapper is told it]; pts
+    (R, S, 3), else ro (R, 3) and z (R, S); code_index (R,) int64, else one code row or one per ray; 10 and 4
+    frequencies -> (rd, pts, ro, z, code_index, R, fx, fd): the tensors contiguous, fx / fd the host arrays."""
+    rd = _cuda(rd, "rd")
+    assert rd.dim() == 2 and rd.shape[1] == 3, "rd must be (num_rays, 3)"
+    n = rd.shape[0]
+    assert n_rays is None or n == n_rays, "rd must have one row per ray"
+    if pts is not None:
+        pts, ro, z = _cuda(pts, "pts"), _opt(ro, "ro"), _opt(z, "z")
+        assert pts.shape == (n, n_samples, 3), "pts must be (num_rays, num_samples, 3)"
+    else:
+        ro, z = _cuda(ro, "ro"), _cuda(z, "z")
+        assert ro.shape == (n, 3) and z.shape == (n, n_samples), \
+            "ro must be (num_rays, 3) and z (num_rays, num_samples)"
+    code_index = _code_rows(code_index, n_codes, n)
+    return rd, pts, ro, z, code_index, n, _freqs(freqs_xyz, 10, "freqs_xyz"), _freqs(freqs_dir, 4, "freqs_dir")
+
+
+def _point_inputs(freqs_xyz: Sequence[float], pts: Optional[Tensor], ro: Optional[Tensor], rd: Optional[Tensor],
+                  z: Optional[Tensor], x: Optional[Tensor], code_index: Optional[Tensor], n_codes: int):
+    """The density entries' form, checked: exactly one of pts (R, S, 3) or (M, 3) [R = M, S = 1]; ro, rd
+    (R, 3) with z (R, S); x (M, 63) or (M, 90) encoded rows [R = M, S = 1]; the codes as in _ray_inputs; 10
+    frequencies -> (pts, ro, rd, z, x, code_index, lead, R, S, fx): ``lead`` the outputs' leading shape."""
+    modes = (pts is not None) + (x is not None) + (ro is not None or rd is not None or z is not None)
+    assert modes == 1, "give exactly one of pts, (ro, rd, z) and x"
+    if pts is not None:
+        pts = _cuda(pts, "pts")
+        assert pts.dim() in (2, 3) and pts.shape[-1] == 3, "pts must be (num_rays, num_samples, 3) or (M, 3)"
+        lead = tuple(pts.shape[:-1])
+    elif x is not None:
+        x = _cuda(x, "x")
+        assert x.dim() == 2 and x.shape[1] in (63, 90), "x must be (M, 63) or (M, 63 + 27)"
+        lead = (x.shape[0],)
+    else:
+        assert ro is not None and rd is not None and z is not None, "the ray form takes ro, rd and z"
+        ro, rd, z = _cuda(ro, "ro"), _cuda(rd, "rd"), _cuda(z, "z")
+        assert z.dim() == 2 and ro.shape == (z.shape[0], 3) and rd.shape == (z.shape[0], 3), \
+            "ro / rd must be (num_rays, 3) and z (num_rays, num_samples)"
+        lead = tuple(z.shape)
+    n, s = lead[0], (lead[1] if len(lead) == 2 else 1)
+    return pts, ro, rd, z, x, _code_rows(code_index, n_codes, n), lead, n, s, _freqs(freqs_xyz, 10, "freqs_xyz")
 
 
 # ------------------------------------------------------------------ rays
@@ -476,20 +548,9 @@ def radiance_field(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int, chunk
     lib = _lib_ready()
     fold = _fold_rows(precision, cb, fold_bias)
     assert not view_rows or fold is not None, "view_rows goes with precision 'f32_w16_fold'"
-    rd = _cuda(rd, "rd")
-    n = rd.shape[0]
-    if pts is not None:
-        pts = _cuda(pts, "pts")
-        assert pts.shape == (n, n_samples, 3), "pts must be (num_rays, num_samples, 3)"
-    else:
-        ro, z = _cuda(ro, "ro"), _cuda(z, "z")
-        assert z.shape == (n, n_samples)
     n_codes = cb.shape[0]
-    if code_index is not None:
-        code_index = _cuda(code_index, "code_index", torch.int64)
-    else:
-        assert n_codes in (1, n), "codes must be one row or one row per ray"
-    assert len(freqs_xyz) == 10 and len(freqs_dir) == 4, "the field kernel implements L_xyz=10, L_dir=4"
+    rd, pts, ro, z, code_index, n, fx, fd = _ray_inputs(rd, n_samples, freqs_xyz, freqs_dir, pts, ro, z, code_index,
+                                                        n_codes)
     raw = torch.empty(n, n_samples, 4, device=rd.device, dtype=torch.float32)
     one_code = n_codes == 1 and code_index is None
     if view_rows is None:
@@ -501,18 +562,16 @@ def radiance_field(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int, chunk
     if n and fold is not None and view_rows:
         rows = _view_rows_table(packed, fold, rd, freqs_dir)
         check(lib.cn_radiance_field_fold_rows(ptr(packed), _fmt(precision), ptr(cb), ptr(fold), ptr(rows), None, 1,
-                                              ptr(pts), ptr(ro), ptr(rd), ptr(z), n, n_samples, chunk_rows,
-                                              _lib.host_floats(freqs_xyz), _lib.host_floats(freqs_dir), ptr(raw),
-                                              stream_of(rd)), "cn_radiance_field_fold_rows")
+                                              ptr(pts), ptr(ro), ptr(rd), ptr(z), n, n_samples, chunk_rows, fx, fd,
+                                              ptr(raw), stream_of(rd)), "cn_radiance_field_fold_rows")
     elif n and fold is not None:
         check(lib.cn_radiance_field_fold(ptr(packed), _fmt(precision), ptr(cb), ptr(fold), ptr(code_index), n_codes,
-                                         ptr(pts), ptr(ro), ptr(rd), ptr(z), n, n_samples, chunk_rows,
-                                         _lib.host_floats(freqs_xyz), _lib.host_floats(freqs_dir), ptr(raw),
-                                         stream_of(rd)), "cn_radiance_field_fold")
+                                         ptr(pts), ptr(ro), ptr(rd), ptr(z), n, n_samples, chunk_rows, fx, fd,
+                                         ptr(raw), stream_of(rd)), "cn_radiance_field_fold")
     elif n:
         check(lib.cn_radiance_field(ptr(packed), _fmt(precision), ptr(cb), ptr(code_index), n_codes, ptr(pts), ptr(ro),
-                                    ptr(rd), ptr(z), n, n_samples, chunk_rows, _lib.host_floats(freqs_xyz),
-                                    _lib.host_floats(freqs_dir), ptr(raw), stream_of(rd)), "cn_radiance_field")
+                                    ptr(rd), ptr(z), n, n_samples, chunk_rows, fx, fd, ptr(raw), stream_of(rd)),
+              "cn_radiance_field")
     return raw
 
 
@@ -530,38 +589,14 @@ def density_field(packed: Tensor, cb: Tensor, freqs_xyz: Sequence[float], *, pts
     sample_pdf take), or (sigma, raw) when both are asked for."""
     lib = _lib_ready()
     assert want_sigma or want_raw, "ask for sigma, raw or both"
-    modes = (pts is not None) + (x is not None) + (ro is not None or rd is not None or z is not None)
-    assert modes == 1, "give exactly one of pts, (ro, rd, z) and x"
-    x_stride = 0
-    if pts is not None:
-        pts = _cuda(pts, "pts")
-        assert pts.dim() in (2, 3) and pts.shape[-1] == 3, "pts must be (num_rays, num_samples, 3) or (M, 3)"
-        lead = tuple(pts.shape[:-1])
-        dev = pts.device
-    elif x is not None:
-        x = _cuda(x, "x")
-        assert x.dim() == 2 and x.shape[1] in (63, 90), "x must be (M, 63) or (M, 63 + 27)"
-        lead, x_stride, dev = (x.shape[0],), x.shape[1], x.device
-    else:
-        assert ro is not None and rd is not None and z is not None, "the ray form takes ro, rd and z"
-        ro, rd, z = _cuda(ro, "ro"), _cuda(rd, "rd"), _cuda(z, "z")
-        assert z.dim() == 2 and ro.shape == (z.shape[0], 3) and rd.shape == (z.shape[0], 3), \
-            "ro / rd must be (num_rays, 3) and z (num_rays, num_samples)"
-        lead, dev = tuple(z.shape), z.device
-    n = lead[0]
-    s = lead[1] if len(lead) == 2 else 1
     n_codes = cb.shape[0]
-    if code_index is not None:
-        code_index = _cuda(code_index, "code_index", torch.int64)
-        assert code_index.shape == (n,), "code_index must be (num_rays,)"
-    else:
-        assert n_codes in (1, n), "codes must be one row or one row per ray"
-    assert len(freqs_xyz) == 10, "the field kernel implements L_xyz=10"
+    pts, ro, rd, z, x, code_index, lead, n, s, fx = _point_inputs(freqs_xyz, pts, ro, rd, z, x, code_index, n_codes)
+    dev = (pts if pts is not None else x if x is not None else z).device
     sigma = torch.empty(lead, device=dev, dtype=torch.float32) if want_sigma else None
     raw = torch.empty(lead + (4,), device=dev, dtype=torch.float32) if want_raw else None
     if n * s:      # no samples: empty outputs without a launch (the C ABI refuses sizes of 0)
         check(lib.cn_density_field(ptr(packed), _lib.CN_FMT_F32_W16, ptr(cb), ptr(code_index), n_codes, ptr(pts),
-                                   ptr(ro), ptr(rd), ptr(z), ptr(x), x_stride, n, s, _lib.host_floats(freqs_xyz),
+                                   ptr(ro), ptr(rd), ptr(z), ptr(x), 0 if x is None else x.shape[1], n, s, fx,
                                    ptr(sigma), ptr(raw), stream_of(cb)), "cn_density_field")
     if want_sigma and want_raw:
         return sigma, raw
@@ -580,33 +615,13 @@ def density_gradient(packed: Tensor, packed_t: Tensor, cb: Tensor, freqs_xyz: Se
     ``packed_t``: the "f32_w16_t" pack of the same parameters; ``cb`` one code row, one per R, or rows picked
     by ``code_index`` (R,)."""
     lib = _lib_ready()
-    modes = (pts is not None) + (ro is not None or rd is not None or z is not None)
-    assert modes == 1, "give exactly one of pts and (ro, rd, z)"
-    if pts is not None:
-        pts = _cuda(pts, "pts")
-        assert pts.dim() in (2, 3) and pts.shape[-1] == 3, "pts must be (num_rays, num_samples, 3) or (M, 3)"
-        lead = tuple(pts.shape[:-1])
-        dev = pts.device
-    else:
-        assert ro is not None and rd is not None and z is not None, "the ray form takes ro, rd and z"
-        ro, rd, z = _cuda(ro, "ro"), _cuda(rd, "rd"), _cuda(z, "z")
-        assert z.dim() == 2 and ro.shape == (z.shape[0], 3) and rd.shape == (z.shape[0], 3), \
-            "ro / rd must be (num_rays, 3) and z (num_rays, num_samples)"
-        lead, dev = tuple(z.shape), z.device
-    n = lead[0]
-    s = lead[1] if len(lead) == 2 else 1
     n_codes = cb.shape[0]
-    if code_index is not None:
-        code_index = _cuda(code_index, "code_index", torch.int64)
-        assert code_index.shape == (n,), "code_index must be (num_rays,)"
-    else:
-        assert n_codes in (1, n), "codes must be one row or one row per ray"
-    assert len(freqs_xyz) == 10, "the field kernel implements L_xyz=10"
-    out = torch.empty(lead + (4,), device=dev, dtype=torch.float32)
+    pts, ro, rd, z, _, code_index, lead, n, s, fx = _point_inputs(freqs_xyz, pts, ro, rd, z, None, code_index, n_codes)
+    out = torch.empty(lead + (4,), device=(pts if pts is not None else z).device, dtype=torch.float32)
     if n * s:      # no samples: an empty output without a launch (the C ABI refuses sizes of 0)
         check(lib.cn_density_gradient(ptr(packed), ptr(packed_t), _lib.CN_FMT_F32_W16, _lib.CN_FMT_F32_W16_T, ptr(cb),
-                                      ptr(code_index), n_codes, ptr(pts), ptr(ro), ptr(rd), ptr(z), n, s,
-                                      _lib.host_floats(freqs_xyz), ptr(out), stream_of(cb)), "cn_density_gradient")
+                                      ptr(code_index), n_codes, ptr(pts), ptr(ro), ptr(rd), ptr(z), n, s, fx,
+                                      ptr(out), stream_of(cb)), "cn_density_gradient")
     return out
 
 
@@ -824,10 +839,6 @@ def scatter_rgb(raw_compact: Tensor, sample_index: Tensor, raw: Tensor) -> Tenso
 # ------------------------------------------------------------------ backward (A14)
 
 
-def _opt(t: Optional[Tensor], name: str) -> Optional[Tensor]:
-    return None if t is None else _cuda(t, name)
-
-
 def volume_render_backward(raw: Tensor, z: Tensor, rd: Tensor, g_rgb=None, g_disp=None, g_acc=None,
                            g_weights=None, g_depth=None, want_rd: bool = True,
                            d_rd_into: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
@@ -890,23 +901,14 @@ def radiance_field_train(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int,
                          code_index: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """fp32 radiance_field that also keeps the activations -> raw (R,S,4), saved (5, R*S, 256)."""
     lib = _lib_ready()
-    rd = _cuda(rd, "rd")
-    n = rd.shape[0]
-    if pts is not None:
-        pts = _cuda(pts, "pts")
-        assert pts.shape == (n, n_samples, 3)
-    else:
-        ro, z = _cuda(ro, "ro"), _cuda(z, "z")
-        assert z.shape == (n, n_samples)
-    if code_index is not None:
-        code_index = _cuda(code_index, "code_index", torch.int64)
+    rd, pts, ro, z, code_index, n, fx, fd = _ray_inputs(rd, n_samples, freqs_xyz, freqs_dir, pts, ro, z, code_index,
+                                                        cb.shape[0])
     raw = torch.empty(n, n_samples, 4, device=rd.device, dtype=torch.float32)
     saved = torch.empty(5, n * n_samples, 256, device=rd.device, dtype=torch.float32)
     if n * n_samples == 0:
         return raw, saved
     check(lib.cn_radiance_field_train(ptr(packed), ptr(cb), ptr(code_index), cb.shape[0], ptr(pts), ptr(ro), ptr(rd),
-                                      ptr(z), n, n_samples, chunk_rows, _lib.host_floats(freqs_xyz),
-                                      _lib.host_floats(freqs_dir), ptr(raw), ptr(saved), stream_of(rd)),
+                                      ptr(z), n, n_samples, chunk_rows, fx, fd, ptr(raw), ptr(saved), stream_of(rd)),
           "cn_radiance_field_train")
     return raw, saved
 
@@ -920,16 +922,8 @@ def radiance_field_train_w16(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: 
     kernel (packed "bf16x3")."""
     fmt = _lib.CN_FMT_BF16X3 if precision == "bf16x3" else _lib.CN_FMT_F32_W16
     lib = _lib_ready()
-    rd = _cuda(rd, "rd")
-    n = rd.shape[0]
-    if pts is not None:
-        pts = _cuda(pts, "pts")
-        assert pts.shape == (n, n_samples, 3)
-    else:
-        ro, z = _cuda(ro, "ro"), _cuda(z, "z")
-        assert z.shape == (n, n_samples)
-    if code_index is not None:
-        code_index = _cuda(code_index, "code_index", torch.int64)
+    rd, pts, ro, z, code_index, n, fx, fd = _ray_inputs(rd, n_samples, freqs_xyz, freqs_dir, pts, ro, z, code_index,
+                                                        cb.shape[0])
     m = n * n_samples
     raw = torch.empty(n, n_samples, 4, device=rd.device, dtype=torch.float32)
     if m == 0:
@@ -941,9 +935,8 @@ def radiance_field_train_w16(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: 
     saved = buf[:5 * m * 256].view(5, m, 256)
     masks = torch.empty(int(lib.cn_field_mask_words_fmt(fmt, m)), device=rd.device, dtype=torch.int32)
     check(lib.cn_radiance_field_train_fmt(fmt, ptr(packed), ptr(cb), ptr(code_index), cb.shape[0], ptr(pts), ptr(ro),
-                                          ptr(rd), ptr(z), n, n_samples, chunk_rows, _lib.host_floats(freqs_xyz),
-                                          _lib.host_floats(freqs_dir), ptr(raw), ptr(saved), ptr(masks),
-                                          stream_of(rd)), "cn_radiance_field_train_fmt")
+                                          ptr(rd), ptr(z), n, n_samples, chunk_rows, fx, fd, ptr(raw), ptr(saved),
+                                          ptr(masks), stream_of(rd)), "cn_radiance_field_train_fmt")
     return raw, saved, masks
 
 
@@ -991,10 +984,9 @@ def field_backward_train_multi(fields: Sequence[dict], precision: str = "f32"):
                 saved.untyped_storage().nbytes() >= need, \
                 "field_backward_train: saved must be the training forward's own buffer (planes + encoding plane)"
         dev = d_raw.device
-        rd, pts, ro, z = _opt(f["rd"], "rd"), _opt(f.get("pts"), "pts"), _opt(f.get("ro"), "ro"), _opt(f.get("z"), "z")
-        code_index = f.get("code_index")
-        if code_index is not None:
-            code_index = _cuda(code_index, "code_index", torch.int64)
+        rd, pts, ro, z, code_index, _, fx, fd = _ray_inputs(
+            f["rd"], n_samples, f["freqs_xyz"], f["freqs_dir"], f.get("pts"), f.get("ro"), f.get("z"),
+            f.get("code_index"), n_codes, n_rays)
         ws = torch.empty(max(0, int(lib.cn_field_backward_train_workspace_floats(m))), device=dev, dtype=torch.float32)
         g_code = f.get("g_code")
         if g_code is None:
@@ -1013,7 +1005,6 @@ def field_backward_train_multi(fields: Sequence[dict], precision: str = "f32"):
         if pg is not None:
             assert len(pg) == _lib.CN_NUM_PARAMS and all(g.is_contiguous() for g in pg)
             garr, k2 = _lib.pointer_array(list(pg))
-        fx, fd = _lib.host_floats(f["freqs_xyz"]), _lib.host_floats(f["freqs_dir"])
         keep += [params, d_raw, ws, arr, k1, garr, k2, fx, fd, rd, pts, ro, z, code_index]
         structs.append(_lib.FieldTrainBwd(
             ptr(f["packed_t"]), arr, ptr(f["masks"]), ptr(saved), ptr(x_enc), ptr(d_raw), ptr(pts), ptr(ro), ptr(rd),
@@ -1049,15 +1040,12 @@ def encode_inputs(rd: Tensor, n_samples: int, chunk_rows: int, freqs_xyz: Sequen
                   z: Optional[Tensor] = None) -> Tensor:
     """forward_pass's MLP input rows (nerf/__init__.py:116-132) -> (R*S, 90)."""
     lib = _lib_ready()
-    rd = _cuda(rd, "rd")
-    n = rd.shape[0]
-    pts, ro, z = _opt(pts, "pts"), _opt(ro, "ro"), _opt(z, "z")
+    rd, pts, ro, z, _, n, fx, fd = _ray_inputs(rd, n_samples, freqs_xyz, freqs_dir, pts, ro, z, None, None)
     x = torch.empty(n * n_samples, 90, device=rd.device, dtype=torch.float32)
     if n * n_samples == 0:
         return x
-    check(lib.cn_encode_inputs(ptr(pts), ptr(ro), ptr(rd), ptr(z), n, n_samples, chunk_rows,
-                               _lib.host_floats(freqs_xyz), _lib.host_floats(freqs_dir), ptr(x), stream_of(rd)),
-          "cn_encode_inputs")
+    check(lib.cn_encode_inputs(ptr(pts), ptr(ro), ptr(rd), ptr(z), n, n_samples, chunk_rows, fx, fd, ptr(x),
+                               stream_of(rd)), "cn_encode_inputs")
     return x
 
 
@@ -1079,10 +1067,15 @@ def field_backward(params: Sequence[Tensor], saved: Tensor, x_enc: Tensor, d_raw
     d_raw = _aligned16(_cuda(d_raw, "d_raw"))
     assert d_raw.numel() == 4 * m and saved.shape == (5, m, 256) and (x_enc is None or x_enc.shape == (m, 90))
     dev = d_raw.device
-    rd, pts, ro, z = _opt(rd, "rd"), _opt(pts, "pts"), _opt(ro, "ro"), _opt(z, "z")
-    if code_index is not None:
-        code_index = _cuda(code_index, "code_index", torch.int64)
-    ws = torch.empty(max(0, int(lib.cn_field_backward_workspace_floats(m))), device=dev, dtype=torch.float32)
+    if rd is not None:
+        rd, pts, ro, z, code_index, _, fx, fd = _ray_inputs(rd, n_samples, freqs_xyz, freqs_dir, pts, ro, z, code_index,
+                                                            n_codes, n_rays)
+    else:       # no ray gradient wanted (encoded rows, or points alone): the C side's own rules
+        pts, ro, z = _opt(pts, "pts"), _opt(ro, "ro"), _opt(z, "z")
+        code_index = None if code_index is None else _cuda(code_index, "code_index", torch.int64)
+        fx = _lib.host_floats(freqs_xyz) if freqs_xyz is not None else None
+        fd = _lib.host_floats(freqs_dir) if freqs_dir is not None else None
+    ws =torch.empty(max(0, int(lib.cn_field_backward_workspace_floats(m))), device=dev, dtype=torch.float32)
     out = {}
     g_code = torch.zeros(n_codes, _lib.CN_CODE_BIAS_STRIDE, device=dev, dtype=torch.float32) if want_code else None
     d_pts = torch.empty(n_rays, n_samples, 3, device=dev, dtype=torch.float32) if want_pts else None
@@ -1098,8 +1091,6 @@ def field_backward(params: Sequence[Tensor], saved: Tensor, x_enc: Tensor, d_raw
     if param_grads is not None:
         assert len(param_grads) == _lib.CN_NUM_PARAMS and all(g.is_contiguous() for g in param_grads)
         garr, gkeep = _lib.pointer_array(list(param_grads))
-    fx = _lib.host_floats(freqs_xyz) if freqs_xyz is not None else None
-    fd = _lib.host_floats(freqs_dir) if freqs_dir is not None else None
     check(lib.cn_field_backward_fmt(_lib.FORMATS[precision], arr, ptr(saved), ptr(x_enc), ptr(d_raw), ptr(pts), ptr(ro), ptr(rd), ptr(z), n_rays,
                                 n_samples, chunk_rows, ptr(code_index), n_codes, fx, fd, ptr(ws), garr, ptr(g_code),
                                 ptr(d_pts), ptr(d_ro), ptr(d_rd), stream_of(d_raw)), "cn_field_backward_fmt")
@@ -1298,25 +1289,16 @@ def radiance_field_masks(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int,
     16x16x4 kernel)."""
     fmt = _lib.CN_FMT_BF16X3 if precision == "bf16x3" else _lib.CN_FMT_F32_W16
     lib = _lib_ready()
-    rd = _cuda(rd, "rd")
-    n = rd.shape[0]
-    if pts is not None:
-        pts = _cuda(pts, "pts")
-        assert pts.shape == (n, n_samples, 3)
-    else:
-        ro, z = _cuda(ro, "ro"), _cuda(z, "z")
-        assert z.shape == (n, n_samples)
-    if code_index is not None:
-        code_index = _cuda(code_index, "code_index", torch.int64)
+    rd, pts, ro, z, code_index, n, fx, fd = _ray_inputs(rd, n_samples, freqs_xyz, freqs_dir, pts, ro, z, code_index,
+                                                        cb.shape[0])
     m = n * n_samples
     raw = torch.empty(n, n_samples, 4, device=rd.device, dtype=torch.float32)
     if m == 0:
         return raw, torch.empty(0, device=rd.device, dtype=torch.int32)
     masks = torch.empty(int(lib.cn_field_mask_words_fmt(fmt, m)), device=rd.device, dtype=torch.int32)
     check(lib.cn_radiance_field_masks_fmt(fmt, ptr(packed), ptr(cb), ptr(code_index), cb.shape[0], ptr(pts), ptr(ro),
-                                          ptr(rd), ptr(z), n, n_samples, chunk_rows, _lib.host_floats(freqs_xyz),
-                                          _lib.host_floats(freqs_dir), ptr(raw), ptr(masks), stream_of(rd)),
-          "cn_radiance_field_masks_fmt")
+                                          ptr(rd), ptr(z), n, n_samples, chunk_rows, fx, fd, ptr(raw), ptr(masks),
+                                          stream_of(rd)), "cn_radiance_field_masks_fmt")
     return raw, masks
 
 
@@ -1352,9 +1334,8 @@ def field_backward_x3(packed_t: Tensor, masks: Tensor, d_raw: Tensor, n_rays: in
     d_raw = _aligned16(_cuda(d_raw, "d_raw"))
     assert d_raw.numel() == 4 * m
     dev = d_raw.device
-    rd, pts, ro, z = _opt(rd, "rd"), _opt(pts, "pts"), _opt(ro, "ro"), _opt(z, "z")
-    if code_index is not None:
-        code_index = _cuda(code_index, "code_index", torch.int64)
+    rd, pts, ro, z, code_index, _, fx, fd = _ray_inputs(rd, n_samples, freqs_xyz, freqs_dir, pts, ro, z, code_index,
+                                                        n_codes, n_rays)
     # the accumulated outputs share one zero-filled buffer (one fill launch instead of three)
     nc = n_codes * _lib.CN_CODE_BIAS_STRIDE
     n_acc = field_backward_x3_acc_floats(n_codes, n_rays, want_ro, want_rd)
@@ -1378,9 +1359,8 @@ def field_backward_x3(packed_t: Tensor, masks: Tensor, d_raw: Tensor, n_rays: in
         ws = torch.empty(int(lib.cn_field_backward_fused_workspace_floats(fmt_t, n_rays, n_samples)), device=dev,
                          dtype=torch.float32)
     check(lib.cn_field_backward_fused_ws(fmt_t, ptr(packed_t), ptr(masks), ptr(d_raw), ptr(pts), ptr(ro), ptr(rd),
-                                         ptr(z), n_rays, n_samples, chunk_rows, ptr(code_index), n_codes,
-                                         _lib.host_floats(freqs_xyz), _lib.host_floats(freqs_dir), ptr(g_code),
-                                         ptr(d_pts), ptr(d_ro), ptr(d_rd), ptr(ws), stream_of(d_raw)),
+                                         ptr(z), n_rays, n_samples, chunk_rows, ptr(code_index), n_codes, fx, fd,
+                                         ptr(g_code), ptr(d_pts), ptr(d_ro), ptr(d_rd), ptr(ws), stream_of(d_raw)),
           "cn_field_backward_fused_ws")
     return {"g_code": g_code, "d_pts": d_pts, "d_ro": d_ro, "d_rd": d_rd}
 
@@ -1404,7 +1384,8 @@ def field_backward_x3_multi(fields: Sequence[dict], d_rd_between: Optional[Tenso
         d_raw = _aligned16(_cuda(f["d_raw"], "d_raw"))
         assert d_raw.numel() == 4 * m and m > 0
         dev = d_raw.device
-        rd, ro, z = _opt(f["rd"], "rd"), _opt(f.get("ro"), "ro"), _opt(f.get("z"), "z")
+        rd, _, ro, z, _, _, fx, fd = _ray_inputs(f["rd"], n_samples, f["freqs_xyz"], f["freqs_dir"], None, f.get("ro"),
+                                                 f.get("z"), None, 1, n_rays)
         acc = f["acc"]
         assert acc.numel() == field_backward_x3_acc_floats(n_codes, n_rays, True, True) and acc.is_contiguous()
         g_code = acc[:_lib.CN_CODE_BIAS_STRIDE].view(1, _lib.CN_CODE_BIAS_STRIDE)
@@ -1412,7 +1393,6 @@ def field_backward_x3_multi(fields: Sequence[dict], d_rd_between: Optional[Tenso
         assert all(t.is_cuda and t.is_contiguous() and t.shape == (n_rays, 3) for t in (d_ro, d_rd))
         ws = torch.empty(int(lib.cn_field_backward_fused_workspace_floats(fmt_t, n_rays, n_samples)), device=dev,
                          dtype=torch.float32)
-        fx, fd = _lib.host_floats(f["freqs_xyz"]), _lib.host_floats(f["freqs_dir"])
         keep += [d_raw, rd, ro, z, ws, fx, fd]
         structs.append(_lib.FieldFusedBwd(
             ptr(f["packed_t"]), ptr(f["masks"]), ptr(d_raw), None, ptr(ro), ptr(rd), ptr(z), n_rays, n_samples,

@@ -11,6 +11,12 @@
     if (!(cond)) return CN_EINVAL;  \
   } while (0)
 
+#define CN_TRY(x)                 \
+  do {                            \
+    const int rc_ = (x);          \
+    if (rc_ != CN_OK) return rc_; \
+  } while (0)
+
 namespace cn {
 
 constexpr int kWave = 64;

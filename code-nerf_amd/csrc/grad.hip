@@ -2711,12 +2711,6 @@ int seg_sum(const float* A, int64_t lda, int64_t M, int N, int64_t S, const int6
   return launch_status();
 }
 
-#define CN_TRY(x)              \
-  do {                         \
-    const int rc_ = (x);       \
-    if (rc_ != CN_OK) return rc_; \
-  } while (0)
-
 }  // namespace
 
 extern "C" int cn_gemm_nn(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
@@ -2763,19 +2757,10 @@ extern "C" int cn_gemm_tn_x3(const float* A, int64_t lda, const float* B, int64_
 extern "C" int cn_encode_inputs(const float* pts, const float* ro, const float* rd, const float* z, int64_t n_rays,
                                 int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz, const float* freqs_dir,
                                 float* x, cn_stream_t stream) {
-  CN_CHECK_ARG(rd && x && freqs_xyz && freqs_dir && (pts || (ro && z)));
-  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && chunk_rows > 0);
-  mlp::FieldArgs a = {};
-  a.pts = pts;
-  a.ro = ro;
-  a.rd = rd;
-  a.z = z;
-  a.n_rays = n_rays;
-  a.n_samples = n_samples;
-  a.chunk_rows = chunk_rows;
-  a.m = n_rays * n_samples;
-  for (int i = 0; i < 10; ++i) a.fx[i] = freqs_xyz[i];
-  for (int i = 0; i < 4; ++i) a.fd[i] = freqs_dir[i];
+  CN_CHECK_ARG(x);
+  const mlp::FieldInputs in = {pts, ro, rd, z, n_rays, n_samples, chunk_rows, nullptr, 0, freqs_xyz, freqs_dir};
+  mlp::FieldArgs a;
+  CN_TRY(mlp::field_args(in, mlp::kEncodeForm, 0, a));
   hipLaunchKernelGGL(grad::encode_inputs_kernel, dim3(elementwise_grid(a.m * 90, 256)), dim3(256), 0,
                      as_stream(stream), a, x);
   return launch_status();
@@ -3283,44 +3268,49 @@ extern "C" int64_t cn_field_backward_fused_workspace_floats(int fmt_t, int64_t n
   return fused_ws_layout(row ? row : 32, n_rays * n_samples, nullptr, nullptr, nullptr);
 }
 
-extern "C" int cn_field_backward_fused_ws(int fmt_t, const float* packed_t, const uint32_t* masks,
-                                          const float* d_raw, const float* pts, const float* ro, const float* rd,
-                                          const float* z, int64_t n_rays, int64_t n_samples, int64_t chunk_rows,
-                                          const int64_t* code_index, int64_t n_codes, const float* freqs_xyz,
-                                          const float* freqs_dir, float* g_code, float* d_pts, float* d_ro,
-                                          float* d_rd, float* workspace, cn_stream_t stream) {
+// cn_field_backward_fused_ws on its arguments as one struct (a field of cn_field_backward_fused_multi).
+static int fused_backward_ws(int fmt_t, const cn_field_fused_bwd& f, hipStream_t st) {
   mlp::FieldArgs a;
-  CN_TRY(mlp::fused_backward_args(fmt_t, packed_t, masks, d_raw, pts, ro, rd, z, n_rays, n_samples, chunk_rows,
-                                  code_index, n_codes, freqs_xyz, freqs_dir, g_code, d_pts, d_ro, d_rd, a));
-  hipStream_t st = as_stream(stream);
-  const int mode = pts ? mlp::kFromPts : mlp::kFromRayZ;
+  CN_TRY(mlp::fused_backward_args(fmt_t, f, a));
+  const int mode = f.pts ? mlp::kFromPts : mlp::kFromRayZ;
   const bool x3 = fmt_t == CN_FMT_BF16X3_T;
   // the deterministic form needs one code row (g_code: one row per workgroup) and ray rows: a wave's with
   // every wave inside one ray, else (fp32) a sample's; otherwise the float-atomic kernel
-  const int wave_samples = fused_ray_row_samples(fmt_t, n_samples);
-  const bool det = workspace && n_codes == 1 && wave_samples > 0;
+  const int wave_samples = fused_ray_row_samples(fmt_t, f.n_samples);
+  const bool det = f.workspace && f.n_codes == 1 && wave_samples > 0;
   int64_t ray_off = 0, q1_off = 0, rows_off = 0;
   if (det) {
     fused_ws_layout(wave_samples, a.m, &ray_off, &q1_off, &rows_off);
-    a.gc_part = workspace;
-    a.ray_part = mode == mlp::kFromRayZ && (d_ro || d_rd) ? workspace + ray_off : nullptr;
-    a.q1_part = d_rd ? workspace + q1_off : nullptr;
-    if (!x3) a.gc_rows = workspace + rows_off;  // the fp32 kernel adds its waves' rows itself
+    a.gc_part = f.workspace;
+    a.ray_part = mode == mlp::kFromRayZ && (f.d_ro || f.d_rd) ? f.workspace + ray_off : nullptr;
+    a.q1_part = f.d_rd ? f.workspace + q1_off : nullptr;
+    if (!x3) a.gc_rows = f.workspace + rows_off;  // the fp32 kernel adds its waves' rows itself
   }
   CN_TRY(x3 ? mlp::launch_field_x3_bwd(mode, a, st) : mlp::launch_field_w16_bwd(mode, a, st));
   if (!det) return CN_OK;
   // one launch: the rays' sums; each workgroup's wave rows added in wave order (gc_rows: the fp32
   // kernel's own tail, x3 here); g_code += those rows in block order (the dW GEMMs' fixed-order
   // reduction: here for fp32, a launch of its own after this one for x3)
-  float* gc_rows = workspace + rows_off;
-  const int64_t ray_blocks = a.ray_part || a.q1_part ? ceil_div(n_rays, 4) : 0;
-  const grad::GcFinal fin = gc_final(x3 ? nullptr : gc_rows, a.n_blocks, g_code);
+  float* gc_rows = f.workspace + rows_off;
+  const int64_t ray_blocks = a.ray_part || a.q1_part ? ceil_div(f.n_rays, 4) : 0;
+  const grad::GcFinal fin = gc_final(x3 ? nullptr : gc_rows, a.n_blocks, f.g_code);
   const int64_t row_blocks = x3 ? a.n_blocks : 0;
   hipLaunchKernelGGL(grad::ray_grad_reduce_kernel, dim3(static_cast<unsigned>(ray_blocks + row_blocks + fin.blocks)),
-                     dim3(256), 0, st, a.ray_part, a.q1_part, ray_blocks ? n_rays : 0, n_samples, chunk_rows,
-                     wave_samples, d_ro, d_rd, a.gc_part, 4, gc_rows, row_blocks, fin);
+                     dim3(256), 0, st, a.ray_part, a.q1_part, ray_blocks ? f.n_rays : 0, f.n_samples, f.chunk_rows,
+                     wave_samples, f.d_ro, f.d_rd, a.gc_part, 4, gc_rows, row_blocks, fin);
   CN_TRY(launch_status());
-  return x3 ? reduce(nullptr, gc_rows, a.n_blocks, 1, mlp::kCbStride, g_code, mlp::kCbStride, st) : CN_OK;
+  return x3 ? reduce(nullptr, gc_rows, a.n_blocks, 1, mlp::kCbStride, f.g_code, mlp::kCbStride, st) : CN_OK;
+}
+
+extern "C" int cn_field_backward_fused_ws(int fmt_t, const float* packed_t, const uint32_t* masks,
+                                          const float* d_raw, const float* pts, const float* ro, const float* rd,
+                                          const float* z, int64_t n_rays, int64_t n_samples, int64_t chunk_rows,
+                                          const int64_t* code_index, int64_t n_codes, const float* freqs_xyz,
+                                          const float* freqs_dir, float* g_code, float* d_pts, float* d_ro,
+                                          float* d_rd, float* workspace, cn_stream_t stream) {
+  const cn_field_fused_bwd f = {packed_t, masks, d_raw, pts, ro, rd, z, n_rays, n_samples, chunk_rows, code_index,
+                                n_codes, freqs_xyz, freqs_dir, g_code, d_pts, d_ro, d_rd, workspace};
+  return fused_backward_ws(fmt_t, f, as_stream(stream));
 }
 
 // A render's two fields' deterministic eval backwards (the eval step's coarse and fine fields on the same
@@ -3334,11 +3324,7 @@ extern "C" int cn_field_backward_fused_multi(int fmt_t, const cn_field_fused_bwd
                                              const float* d_rd_between, cn_stream_t stream) {
   CN_CHECK_ARG(fields && (n_fields == 1 || n_fields == 2));
   hipStream_t st = as_stream(stream);
-  auto one = [&](const cn_field_fused_bwd& f) {
-    return cn_field_backward_fused_ws(fmt_t, f.packed_t, f.masks, f.d_raw, f.pts, f.ro, f.rd, f.z, f.n_rays,
-                                      f.n_samples, f.chunk_rows, f.code_index, f.n_codes, f.freqs_xyz, f.freqs_dir,
-                                      f.g_code, f.d_pts, f.d_ro, f.d_rd, f.workspace, stream);
-  };
+  auto one = [&](const cn_field_fused_bwd& f) { return fused_backward_ws(fmt_t, f, st); };
   if (n_fields == 1) {
     CN_CHECK_ARG(!d_rd_between);
     return one(fields[0]);
@@ -3353,9 +3339,7 @@ extern "C" int cn_field_backward_fused_multi(int fmt_t, const cn_field_fused_bwd
   if (pair) {
     for (int k = 0; k < 2; ++k) {
       const cn_field_fused_bwd& f = fields[k];
-      CN_TRY(mlp::fused_backward_args(fmt_t, f.packed_t, f.masks, f.d_raw, f.pts, f.ro, f.rd, f.z, f.n_rays,
-                                      f.n_samples, f.chunk_rows, f.code_index, f.n_codes, f.freqs_xyz, f.freqs_dir,
-                                      f.g_code, f.d_pts, f.d_ro, f.d_rd, a[k]));
+      CN_TRY(mlp::fused_backward_args(fmt_t, f, a[k]));
       int64_t ray_off = 0, q1_off = 0, rows_off = 0;
       fused_ws_layout(16, a[k].m, &ray_off, &q1_off, &rows_off);
       a[k].gc_part = f.workspace;
@@ -3456,39 +3440,15 @@ static int train_bwd_setup(int fmt_t, const cn_field_train_bwd& f, TrainBwd& t) 
   using namespace mlp;
   CN_CHECK_ARG(fmt_t == CN_FMT_F32_W16_T || fmt_t == CN_FMT_BF16X3_T);
   t.x3 = fmt_t == CN_FMT_BF16X3_T;
-  CN_CHECK_ARG(f.packed_t && f.params && f.masks && f.saved && f.d_raw && f.rd && f.g_code && f.workspace);
-  CN_CHECK_ARG(f.freqs_xyz && f.freqs_dir && f.n_rays > 0 && f.n_samples > 0 && f.chunk_rows > 0 && f.n_codes > 0);
-  CN_CHECK_ARG(f.pts || (f.ro && f.z));
-  CN_CHECK_ARG(!f.d_pts || f.pts);
-  CN_CHECK_ARG(!f.d_ro || (f.ro && f.z && !f.pts));
-  CN_CHECK_ARG(f.code_index || f.n_codes == 1 || f.n_codes == f.n_rays);
+  CN_CHECK_ARG(f.params && f.saved && f.workspace);
   for (int i = 0; i < CN_NUM_PARAMS; ++i) CN_CHECK_ARG(f.params[i]);
-  // one code row per wave (32 samples x3, 16 samples w16)
-  if (!(f.n_codes == 1 || f.n_samples % (t.x3 ? 32 : 16) == 0)) return CN_EUNSUPPORTED;
-  const int64_t M = f.n_rays * f.n_samples;
-  CN_CHECK_ARG(ceil_div(M, 128) <= 0x7fffffff);
-  CN_CHECK_ARG(cn::aligned16(f.d_raw));  // float4 rows (include/codenerf.h)
+  // the dX chain is the eval backward's: its checks and kernel arguments, plus the dPre planes
+  const cn_field_fused_bwd dx = {f.packed_t, f.masks, f.d_raw, f.pts, f.ro, f.rd, f.z, f.n_rays, f.n_samples,
+                                 f.chunk_rows, f.code_index, f.n_codes, f.freqs_xyz, f.freqs_dir, f.g_code,
+                                 f.d_pts, f.d_ro, f.d_rd, nullptr};
   FieldArgs& a = t.a;
-  a = {};
-  a.packed = f.packed_t;
-  a.code_index = f.code_index;
-  a.n_codes = f.n_codes;
-  a.pts = f.pts;
-  a.ro = f.ro;
-  a.rd = f.rd;
-  a.z = f.z;
-  a.n_rays = f.n_rays;
-  a.n_samples = f.n_samples;
-  a.chunk_rows = f.chunk_rows;
-  a.m = M;
-  for (int i = 0; i < 10; ++i) a.fx[i] = f.freqs_xyz[i];
-  for (int i = 0; i < 4; ++i) a.fd[i] = f.freqs_dir[i];
-  a.masks = const_cast<uint32_t*>(f.masks);
-  a.d_raw = f.d_raw;
-  a.g_code = f.g_code;
-  a.d_pts = f.d_pts;
-  a.d_ro = f.d_ro;
-  a.d_rd = f.d_rd;
+  CN_TRY(fused_backward_args(fmt_t, dx, a));
+  const int64_t M = a.m;
   a.dpre = f.workspace;
   t.mode = f.pts ? kFromPts : kFromRayZ;
   t.saved = f.saved;

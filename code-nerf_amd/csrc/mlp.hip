@@ -343,26 +343,25 @@ __global__ __launch_bounds__(kThreads, 1) void field_kernel(FieldArgs a) {
   }
 }
 
-}  // namespace mlp
-}  // namespace cn
 
-using namespace cn::mlp;
+// ---------------------------------------------------------------- launchers (entry points: field_api.hip)
 
-namespace {
+static_assert(kPackedFloats == 327424, "packed layout changed: update docs");
+static_assert(kCbStride == CN_CODE_BIAS_STRIDE, "code-bias stride mismatch");
 
-int make_params(const float* const* params, Params* P) {
-  if (!params) return CN_EINVAL;
-  for (int i = 0; i < CN_NUM_PARAMS; ++i) {
-    if (!params[i]) return CN_EINVAL;
-    P->p[i] = params[i];
-  }
-  return CN_OK;
+int launch_pack_v1(const Params& P, float* packed, hipStream_t st) {
+  hipLaunchKernelGGL(pack_kernel, dim3(cn::elementwise_grid(kPackedFloats, 256)), dim3(256), 0, st, P, packed);
+  return cn::launch_status();
 }
 
-int launch_field(int fmt, int mode, FieldArgs& a, hipStream_t st) {
-  if (fmt == CN_FMT_BF16X3) return launch_field_x3(mode, a, st);
-  if (fmt == CN_FMT_F32_W16) return launch_field_w16(mode, a, st);
-  if (fmt == CN_FMT_BF16X3_W16) return launch_field_x3w(mode, a, st);
+int launch_code_bias(const Params& P, const float* z_s, const float* z_t, int64_t n_codes, float* out,
+                     hipStream_t st) {
+  hipLaunchKernelGGL(code_bias_kernel, dim3(static_cast<unsigned>(n_codes * kCbSlices)), dim3(kCbThreads), 0, st, P,
+                     z_s, z_t, out);
+  return cn::launch_status();
+}
+
+int launch_field_v1(int mode, FieldArgs& a, hipStream_t st) {
   const unsigned grid = static_cast<unsigned>(cn::ceil_div(a.m, kTile));
   switch (mode) {
     case kFromPts: hipLaunchKernelGGL(field_kernel<kFromPts>, dim3(grid), dim3(kThreads), 0, st, a); break;
@@ -372,532 +371,5 @@ int launch_field(int fmt, int mode, FieldArgs& a, hipStream_t st) {
   return cn::launch_status();
 }
 
-bool valid_fmt(int fmt) {
-  return fmt == CN_FMT_F32 || fmt == CN_FMT_BF16X3 || fmt == CN_FMT_F32_W16 || fmt == CN_FMT_BF16X3_W16;
-}
-bool valid_pack_fmt(int fmt) {
-  return valid_fmt(fmt) || fmt == CN_FMT_BF16X3_T || fmt == CN_FMT_F32_W16_T || fmt == CN_FMT_F32_W16_FOLD;
-}
-
-}  // namespace
-
-static_assert(kPackedFloats == 327424, "packed layout changed: update docs");
-static_assert(kCbStride == CN_CODE_BIAS_STRIDE, "code-bias stride mismatch");
-
-extern "C" int64_t cn_mlp_packed_floats(int fmt) {
-  if (!valid_pack_fmt(fmt)) return -1;
-  if (fmt == CN_FMT_F32_W16 || fmt == CN_FMT_F32_W16_T) return packed_floats_w16();
-  if (fmt == CN_FMT_F32_W16_FOLD) return packed_floats_w16_fold();
-  if (fmt == CN_FMT_BF16X3_W16) return packed_floats_x3w();
-  return fmt == CN_FMT_F32 ? kPackedFloats : packed_floats_x3();
-}
-
-extern "C" int cn_mlp_pack(const float* const* params, int fmt, float* packed, cn_stream_t stream) {
-  Params P;
-  if (make_params(params, &P) != CN_OK || !packed || !valid_pack_fmt(fmt)) return CN_EINVAL;
-  if (fmt == CN_FMT_BF16X3) return launch_pack_x3(P, packed, cn::as_stream(stream));
-  if (fmt == CN_FMT_BF16X3_T) return launch_pack_x3t(P, packed, cn::as_stream(stream));
-  if (fmt == CN_FMT_F32_W16) return launch_pack_w16(P, packed, cn::as_stream(stream));
-  if (fmt == CN_FMT_F32_W16_T) return launch_pack_w16t(P, packed, cn::as_stream(stream));
-  if (fmt == CN_FMT_F32_W16_FOLD) return launch_pack_w16_fold(P, packed, cn::as_stream(stream));
-  if (fmt == CN_FMT_BF16X3_W16) return launch_pack_x3w(P, packed, cn::as_stream(stream));
-  hipLaunchKernelGGL(pack_kernel, dim3(cn::elementwise_grid(kPackedFloats, 256)), dim3(256), 0,
-                     cn::as_stream(stream), P, packed);
-  return cn::launch_status();
-}
-
-extern "C" int cn_code_bias(const float* const* params, const float* z_s, const float* z_t,
-                            int64_t n_codes, float* code_bias, cn_stream_t stream) {
-  Params P;
-  if (make_params(params, &P) != CN_OK) return CN_EINVAL;
-  CN_CHECK_ARG(z_s && z_t && code_bias && n_codes > 0 && n_codes * kCbSlices <= (1ll << 31) - 1);
-  hipLaunchKernelGGL(code_bias_kernel, dim3(static_cast<unsigned>(n_codes * kCbSlices)), dim3(kCbThreads), 0,
-                     cn::as_stream(stream), P, z_s, z_t, code_bias);
-  return cn::launch_status();
-}
-
-extern "C" int cn_fold_bias(const float* const* params, const float* code_bias, int64_t n_codes, float* fold_bias,
-                            cn_stream_t stream) {
-  Params P;
-  if (make_params(params, &P) != CN_OK) return CN_EINVAL;
-  CN_CHECK_ARG(code_bias && fold_bias && n_codes > 0 && n_codes * kFbSlices <= (1ll << 31) - 1);
-  return launch_fold_bias(P, code_bias, n_codes, fold_bias, cn::as_stream(stream));
-}
-
-extern "C" int cn_field_prepare(const float* const* params, const float* z_s, const float* z_t, int64_t n_codes,
-                                float* code_bias, float* packed, float* packed_t, float* zero, int64_t n_zero,
-                                cn_stream_t stream) {
-  const cn_field_prep m = {params, code_bias, packed, packed_t, zero, n_zero, nullptr};
-  return cn_field_prepare_models(&m, 1, z_s, z_t, n_codes, stream);
-}
-
-extern "C" int cn_field_prepare_models(const cn_field_prep* models, int n_models, const float* z_s, const float* z_t,
-                                       int64_t n_codes, cn_stream_t stream) {
-  CN_CHECK_ARG(models && n_models >= 1 && n_models <= 2);
-  PrepareModel pm[2];
-  for (int k = 0; k < n_models; ++k) {
-    const cn_field_prep& m = models[k];
-    if (make_params(m.params, &pm[k].P) != CN_OK) return CN_EINVAL;
-    CN_CHECK_ARG(m.n_zero >= 0 && (m.n_zero == 0 || m.zero));
-    CN_CHECK_ARG(!m.code_bias || (z_s && z_t && n_codes > 0 && n_codes * kCbSlices + 256 <= 0x7fffffff));
-    CN_CHECK_ARG(!m.code_act || m.code_bias);
-    pm[k].code_bias = m.code_bias;
-    pm[k].code_act = m.code_act;
-    pm[k].packed = m.packed;
-    pm[k].packed_t = m.packed_t;
-    pm[k].zero = m.zero;
-    pm[k].n_zero = m.n_zero;
-  }
-  return launch_field_prepare_w16(pm, n_models, z_s, z_t, n_codes, cn::as_stream(stream));
-}
-
-namespace {
-
-// fmt at a forward entry point: the folded pack runs through the *_fold entry points only, and they
-// take no other (CN_EUNSUPPORTED, before any other check and without a launch).
-int forward_fmt_status(int fmt, bool fold_entry) {
-  if (!(valid_fmt(fmt) || fmt == CN_FMT_F32_W16_FOLD)) return CN_EINVAL;
-  return (fmt == CN_FMT_F32_W16_FOLD) == fold_entry ? CN_OK : CN_EUNSUPPORTED;
-}
-
-int launch_field_any(int fmt, int mode, FieldArgs& a, hipStream_t st) {
-  return fmt == CN_FMT_F32_W16_FOLD ? launch_field_w16_fold(mode, a, st) : launch_field(fmt, mode, a, st);
-}
-
-// cn_mlp_forward / cn_mlp_forward_fold (fold_entry: fold_bias required)
-int mlp_forward_any(const float* packed, int fmt, bool fold_entry, const float* code_bias, const float* fold_bias,
-                    const int64_t* code_index, int64_t n_codes, const float* x, int64_t m, float* raw,
-                    cn_stream_t stream) {
-  const int rc = forward_fmt_status(fmt, fold_entry);
-  if (rc != CN_OK) return rc;
-  CN_CHECK_ARG(packed && code_bias && x && raw && m > 0 && n_codes > 0 && (!fold_entry || fold_bias));
-  CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == m);
-  CN_CHECK_ARG(cn::ceil_div(m, kTile) <= 0x7fffffff);
-  FieldArgs a = {};
-  a.packed = packed;
-  a.code_bias = code_bias;
-  a.fold_bias = fold_bias;
-  a.code_index = code_index;
-  a.n_codes = n_codes;
-  a.x = x;
-  a.m = m;
-  a.raw = raw;
-  CN_CHECK_ARG(cn::aligned16(raw));  // float4 rows (include/codenerf.h)
-  CN_CHECK_ARG(cn::aligned16(fold_bias));  // 16-B vector reads of a c_v1 row
-  return launch_field_any(fmt, kFromEncoded, a, cn::as_stream(stream));
-}
-
-// cn_radiance_field / cn_radiance_field_fold
-int radiance_field_any(const float* packed, int fmt, bool fold_entry, const float* code_bias, const float* fold_bias,
-                       const int64_t* code_index, int64_t n_codes, const float* pts, const float* ro,
-                       const float* rd, const float* z, int64_t n_rays, int64_t n_samples, int64_t chunk_rows,
-                       const float* freqs_xyz, const float* freqs_dir, float* raw, cn_stream_t stream) {
-  const int rc = forward_fmt_status(fmt, fold_entry);
-  if (rc != CN_OK) return rc;
-  CN_CHECK_ARG(packed && code_bias && rd && raw && freqs_xyz && freqs_dir && (!fold_entry || fold_bias));
-  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && chunk_rows > 0 && n_codes > 0);
-  CN_CHECK_ARG(pts || (ro && z));
-  CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == n_rays);
-  FieldArgs a = {};
-  a.packed = packed;
-  a.code_bias = code_bias;
-  a.fold_bias = fold_bias;
-  a.code_index = code_index;
-  a.n_codes = n_codes;
-  a.pts = pts;
-  a.ro = ro;
-  a.rd = rd;
-  a.z = z;
-  a.n_rays = n_rays;
-  a.n_samples = n_samples;
-  a.chunk_rows = chunk_rows;
-  a.m = n_rays * n_samples;
-  CN_CHECK_ARG(cn::ceil_div(a.m, kTile) <= 0x7fffffff);
-  for (int i = 0; i < 10; ++i) a.fx[i] = freqs_xyz[i];
-  for (int i = 0; i < 4; ++i) a.fd[i] = freqs_dir[i];
-  a.raw = raw;
-  CN_CHECK_ARG(cn::aligned16(raw));  // float4 rows (include/codenerf.h)
-  CN_CHECK_ARG(cn::aligned16(fold_bias));  // 16-B vector reads of a c_v1 row
-  return launch_field_any(fmt, pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream));
-}
-
-}  // namespace
-
-extern "C" int cn_mlp_forward(const float* packed, int fmt, const float* code_bias,
-                              const int64_t* code_index, int64_t n_codes, const float* x,
-                              int64_t m, float* raw, cn_stream_t stream) {
-  return mlp_forward_any(packed, fmt, false, code_bias, nullptr, code_index, n_codes, x, m, raw, stream);
-}
-
-extern "C" int cn_mlp_forward_fold(const float* packed, int fmt, const float* code_bias, const float* fold_bias,
-                                   const int64_t* code_index, int64_t n_codes, const float* x, int64_t m,
-                                   float* raw, cn_stream_t stream) {
-  return mlp_forward_any(packed, fmt, true, code_bias, fold_bias, code_index, n_codes, x, m, raw, stream);
-}
-
-extern "C" int cn_radiance_field(const float* packed, int fmt, const float* code_bias,
-                                 const int64_t* code_index, int64_t n_codes, const float* pts,
-                                 const float* ro, const float* rd, const float* z, int64_t n_rays,
-                                 int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz,
-                                 const float* freqs_dir, float* raw, cn_stream_t stream) {
-  return radiance_field_any(packed, fmt, false, code_bias, nullptr, code_index, n_codes, pts, ro, rd, z, n_rays,
-                            n_samples, chunk_rows, freqs_xyz, freqs_dir, raw, stream);
-}
-
-extern "C" int cn_radiance_field_fold(const float* packed, int fmt, const float* code_bias, const float* fold_bias,
-                                      const int64_t* code_index, int64_t n_codes, const float* pts,
-                                      const float* ro, const float* rd, const float* z, int64_t n_rays,
-                                      int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz,
-                                      const float* freqs_dir, float* raw, cn_stream_t stream) {
-  return radiance_field_any(packed, fmt, true, code_bias, fold_bias, code_index, n_codes, pts, ro, rd, z, n_rays,
-                            n_samples, chunk_rows, freqs_xyz, freqs_dir, raw, stream);
-}
-
-extern "C" int64_t cn_view_rows_bytes(int64_t n_rays) {
-  return (n_rays > 0 && n_rays <= INT64_MAX / (kHidden * 4)) ? n_rays * kHidden * 4 : -1;
-}
-
-extern "C" int cn_view_rows(const float* packed, int fmt, const float* fold_bias, const float* rd, int64_t n_rays,
-                            const float* freqs_dir, float* view_rows, cn_stream_t stream) {
-  const int rc = forward_fmt_status(fmt, true);
-  if (rc != CN_OK) return rc;
-  CN_CHECK_ARG(packed && fold_bias && rd && freqs_dir && view_rows);
-  CN_CHECK_ARG(n_rays > 0 && cn_view_rows_bytes(n_rays) > 0);
-  CN_CHECK_ARG(cn::aligned16(packed) && cn::aligned16(fold_bias) && cn::aligned16(view_rows));  // 16-B vector accesses
-  FieldArgs a = {};
-  a.packed = packed;
-  a.fold_bias = fold_bias;
-  a.rd = rd;
-  a.n_rays = n_rays;
-  for (int i = 0; i < 4; ++i) a.fd[i] = freqs_dir[i];
-  return launch_view_rows_w16(a, view_rows, cn::as_stream(stream));
-}
-
-extern "C" int cn_radiance_field_fold_rows(const float* packed, int fmt, const float* code_bias,
-                                           const float* fold_bias, const float* view_rows,
-                                           const int64_t* code_index, int64_t n_codes, const float* pts,
-                                           const float* ro, const float* rd, const float* z, int64_t n_rays,
-                                           int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz,
-                                           const float* freqs_dir, float* raw, cn_stream_t stream) {
-  const int rc = forward_fmt_status(fmt, true);
-  if (rc != CN_OK) return rc;
-  CN_CHECK_ARG(packed && code_bias && fold_bias && view_rows && rd && raw && freqs_xyz && freqs_dir);
-  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && chunk_rows > 0);
-  CN_CHECK_ARG(n_codes == 1 && !code_index);  // the rows hold code row 0's c_v1
-  CN_CHECK_ARG(pts || (ro && z));
-  CN_CHECK_ARG(n_rays <= INT64_MAX / n_samples && cn::ceil_div(n_rays * n_samples, kTile) <= 0x7fffffff);
-  CN_CHECK_ARG(cn_view_rows_bytes(n_rays) > 0);
-  CN_CHECK_ARG(cn::aligned16(raw) && cn::aligned16(fold_bias) && cn::aligned16(view_rows));
-  FieldArgs a = {};
-  a.packed = packed;
-  a.code_bias = code_bias;
-  a.fold_bias = fold_bias;
-  a.view_rows = view_rows;
-  a.n_codes = 1;
-  a.pts = pts;
-  a.ro = ro;
-  a.rd = rd;
-  a.z = z;
-  a.n_rays = n_rays;
-  a.n_samples = n_samples;
-  a.chunk_rows = chunk_rows;
-  a.m = n_rays * n_samples;
-  for (int i = 0; i < 10; ++i) a.fx[i] = freqs_xyz[i];
-  for (int i = 0; i < 4; ++i) a.fd[i] = freqs_dir[i];
-  a.raw = raw;
-  return launch_field_w16_fold_rows(pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream));
-}
-
-extern "C" int cn_density_field(const float* packed, int fmt, const float* code_bias, const int64_t* code_index,
-                                int64_t n_codes, const float* pts, const float* ro, const float* rd, const float* z,
-                                const float* x, int64_t x_stride, int64_t n_rays, int64_t n_samples,
-                                const float* freqs_xyz, float* sigma, float* raw, cn_stream_t stream) {
-  CN_CHECK_ARG(packed && code_bias && freqs_xyz);
-  const bool rays = ro || rd || z;
-  CN_CHECK_ARG((pts ? 1 : 0) + (rays ? 1 : 0) + (x ? 1 : 0) == 1);  // exactly one input mode
-  CN_CHECK_ARG(!rays || (ro && rd && z));
-  CN_CHECK_ARG(sigma || raw);
-  CN_CHECK_ARG(cn::aligned16(raw));  // float4 rows (include/codenerf.h)
-  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && n_codes > 0);
-  CN_CHECK_ARG(n_rays <= INT64_MAX / n_samples && cn::ceil_div(n_rays * n_samples, kTile) <= 0x7fffffff);
-  CN_CHECK_ARG(!x || x_stride >= kDimXyz);
-  CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == n_rays);
-  if (fmt != CN_FMT_F32_W16) return (valid_fmt(fmt) || fmt == CN_FMT_F32_W16_FOLD) ? CN_EUNSUPPORTED : CN_EINVAL;
-  DensityArgs d = {};
-  d.f.packed = packed;
-  d.f.code_bias = code_bias;
-  d.f.code_index = code_index;
-  d.f.n_codes = n_codes;
-  d.f.pts = pts;
-  d.f.ro = ro;
-  d.f.rd = rd;
-  d.f.z = z;
-  d.f.x = x;
-  d.f.n_rays = n_rays;
-  d.f.n_samples = n_samples;
-  d.f.chunk_rows = n_rays;
-  d.f.m = n_rays * n_samples;
-  for (int i = 0; i < 10; ++i) d.f.fx[i] = freqs_xyz[i];
-  d.f.raw = raw;
-  d.sigma = sigma;
-  d.x_stride = x_stride;
-  return launch_density_w16(pts ? kFromPts : (x ? kFromEncoded : kFromRayZ), d, cn::as_stream(stream));
-}
-
-extern "C" int cn_density_gradient(const float* packed, const float* packed_t, int fmt, int fmt_t,
-                                   const float* code_bias, const int64_t* code_index, int64_t n_codes,
-                                   const float* pts, const float* ro, const float* rd, const float* z, int64_t n_rays,
-                                   int64_t n_samples, const float* freqs_xyz, float* grad_sigma,
-                                   cn_stream_t stream) {
-  CN_CHECK_ARG(packed && packed_t && code_bias && freqs_xyz && grad_sigma);
-  const bool rays = ro || rd || z;
-  CN_CHECK_ARG((pts ? 1 : 0) + (rays ? 1 : 0) == 1);  // exactly one input mode
-  CN_CHECK_ARG(!rays || (ro && rd && z));
-  CN_CHECK_ARG(cn::aligned16(grad_sigma));  // float4 rows (include/codenerf.h)
-  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && n_codes > 0);
-  CN_CHECK_ARG(n_rays <= INT64_MAX / n_samples && cn::ceil_div(n_rays * n_samples, kTile) <= 0x7fffffff);
-  CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == n_rays);
-  // fmt a forward format, fmt_t a transposed one (the two swapped, or an unknown value: invalid)
-  CN_CHECK_ARG(valid_fmt(fmt) || fmt == CN_FMT_F32_W16_FOLD);
-  CN_CHECK_ARG(fmt_t == CN_FMT_BF16X3_T || fmt_t == CN_FMT_F32_W16_T);
-  if (fmt != CN_FMT_F32_W16 || fmt_t != CN_FMT_F32_W16_T) return CN_EUNSUPPORTED;
-  DensityArgs d = {};
-  d.f.packed = packed;
-  d.f.code_bias = code_bias;
-  d.f.code_index = code_index;
-  d.f.n_codes = n_codes;
-  d.f.pts = pts;
-  d.f.ro = ro;
-  d.f.rd = rd;
-  d.f.z = z;
-  d.f.n_rays = n_rays;
-  d.f.n_samples = n_samples;
-  d.f.chunk_rows = n_rays;
-  d.f.m = n_rays * n_samples;
-  for (int i = 0; i < 10; ++i) d.f.fx[i] = freqs_xyz[i];
-  d.f.raw = grad_sigma;
-  return launch_density_grad_w16(pts ? kFromPts : kFromRayZ, d, packed_t, cn::as_stream(stream));
-}
-
-extern "C" int cn_radiance_field_train(const float* packed, const float* code_bias, const int64_t* code_index,
-                                       int64_t n_codes, const float* pts, const float* ro, const float* rd,
-                                       const float* z, int64_t n_rays, int64_t n_samples, int64_t chunk_rows,
-                                       const float* freqs_xyz, const float* freqs_dir, float* raw, float* save,
-                                       cn_stream_t stream) {
-  CN_CHECK_ARG(packed && code_bias && rd && raw && save && freqs_xyz && freqs_dir);
-  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && chunk_rows > 0 && n_codes > 0);
-  CN_CHECK_ARG(pts || (ro && z));
-  CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == n_rays);
-  FieldArgs a = {};
-  a.packed = packed;
-  a.code_bias = code_bias;
-  a.code_index = code_index;
-  a.n_codes = n_codes;
-  a.pts = pts;
-  a.ro = ro;
-  a.rd = rd;
-  a.z = z;
-  a.n_rays = n_rays;
-  a.n_samples = n_samples;
-  a.chunk_rows = chunk_rows;
-  a.m = n_rays * n_samples;
-  CN_CHECK_ARG(cn::ceil_div(a.m, kTile) <= 0x7fffffff);
-  for (int i = 0; i < 10; ++i) a.fx[i] = freqs_xyz[i];
-  for (int i = 0; i < 4; ++i) a.fd[i] = freqs_dir[i];
-  a.raw = raw;
-  CN_CHECK_ARG(cn::aligned16(raw));  // float4 rows (include/codenerf.h)
-  a.save = save;
-  return launch_field(CN_FMT_F32, pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream));
-}
-
-extern "C" int cn_mlp_forward_train(const float* packed, const float* code_bias, const int64_t* code_index,
-                                    int64_t n_codes, const float* x, int64_t m, float* raw, float* save,
-                                    cn_stream_t stream) {
-  CN_CHECK_ARG(packed && code_bias && x && raw && save && m > 0 && n_codes > 0);
-  CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == m);
-  CN_CHECK_ARG(cn::ceil_div(m, kTile) <= 0x7fffffff);
-  FieldArgs a = {};
-  a.packed = packed;
-  a.code_bias = code_bias;
-  a.code_index = code_index;
-  a.n_codes = n_codes;
-  a.x = x;
-  a.m = m;
-  a.raw = raw;
-  CN_CHECK_ARG(cn::aligned16(raw));  // float4 rows (include/codenerf.h)
-  a.save = save;
-  return launch_field(CN_FMT_F32, kFromEncoded, a, cn::as_stream(stream));
-}
-
-extern "C" int64_t cn_field_mask_words(int64_t m) { return m > 0 ? mask_words_x3(m) : -1; }
-
-extern "C" int64_t cn_field_mask_words_fmt(int fmt, int64_t m) {
-  if (m <= 0) return -1;
-  if (fmt == CN_FMT_BF16X3) return mask_words_x3(m);
-  if (fmt == CN_FMT_F32_W16) return mask_words_w16(m);
-  return -1;
-}
-
-extern "C" int cn_radiance_field_masks(const float* packed, const float* code_bias, const int64_t* code_index,
-                                       int64_t n_codes, const float* pts, const float* ro, const float* rd,
-                                       const float* z, int64_t n_rays, int64_t n_samples, int64_t chunk_rows,
-                                       const float* freqs_xyz, const float* freqs_dir, float* raw, uint32_t* masks,
-                                       cn_stream_t stream) {
-  return cn_radiance_field_masks_fmt(CN_FMT_BF16X3, packed, code_bias, code_index, n_codes, pts, ro, rd, z, n_rays,
-                                     n_samples, chunk_rows, freqs_xyz, freqs_dir, raw, masks, stream);
-}
-
-extern "C" int cn_radiance_field_masks_fmt(int fmt, const float* packed, const float* code_bias,
-                                           const int64_t* code_index, int64_t n_codes, const float* pts,
-                                           const float* ro, const float* rd, const float* z, int64_t n_rays,
-                                           int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz,
-                                           const float* freqs_dir, float* raw, uint32_t* masks, cn_stream_t stream) {
-  CN_CHECK_ARG(fmt == CN_FMT_BF16X3 || fmt == CN_FMT_F32_W16);
-  CN_CHECK_ARG(packed && code_bias && rd && raw && masks && freqs_xyz && freqs_dir);
-  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && chunk_rows > 0 && n_codes > 0);
-  CN_CHECK_ARG(pts || (ro && z));
-  CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == n_rays);
-  FieldArgs a = {};
-  a.packed = packed;
-  a.code_bias = code_bias;
-  a.code_index = code_index;
-  a.n_codes = n_codes;
-  a.pts = pts;
-  a.ro = ro;
-  a.rd = rd;
-  a.z = z;
-  a.n_rays = n_rays;
-  a.n_samples = n_samples;
-  a.chunk_rows = chunk_rows;
-  a.m = n_rays * n_samples;
-  CN_CHECK_ARG(cn::ceil_div(a.m, kTile) <= 0x7fffffff);
-  for (int i = 0; i < 10; ++i) a.fx[i] = freqs_xyz[i];
-  for (int i = 0; i < 4; ++i) a.fd[i] = freqs_dir[i];
-  a.raw = raw;
-  CN_CHECK_ARG(cn::aligned16(raw));  // float4 rows (include/codenerf.h)
-  a.masks = masks;
-  return fmt == CN_FMT_BF16X3 ? launch_field_x3(pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream))
-                              : launch_field_w16(pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream));
-}
-
-extern "C" int cn_radiance_field_train_w16(const float* packed, const float* code_bias, const int64_t* code_index,
-                                           int64_t n_codes, const float* pts, const float* ro, const float* rd,
-                                           const float* z, int64_t n_rays, int64_t n_samples, int64_t chunk_rows,
-                                           const float* freqs_xyz, const float* freqs_dir, float* raw, float* save,
-                                           uint32_t* masks, cn_stream_t stream) {
-  return cn_radiance_field_train_fmt(CN_FMT_F32_W16, packed, code_bias, code_index, n_codes, pts, ro, rd, z, n_rays,
-                                     n_samples, chunk_rows, freqs_xyz, freqs_dir, raw, save, masks, stream);
-}
-
-extern "C" int cn_radiance_field_train_fmt(int fmt, const float* packed, const float* code_bias,
-                                           const int64_t* code_index, int64_t n_codes, const float* pts,
-                                           const float* ro, const float* rd, const float* z, int64_t n_rays,
-                                           int64_t n_samples, int64_t chunk_rows, const float* freqs_xyz,
-                                           const float* freqs_dir, float* raw, float* save, uint32_t* masks,
-                                           cn_stream_t stream) {
-  CN_CHECK_ARG(fmt == CN_FMT_F32_W16 || fmt == CN_FMT_BF16X3);
-  CN_CHECK_ARG(packed && code_bias && rd && raw && save && masks && freqs_xyz && freqs_dir);
-  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && chunk_rows > 0 && n_codes > 0);
-  CN_CHECK_ARG(pts || (ro && z));
-  CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == n_rays);
-  FieldArgs a = {};
-  a.packed = packed;
-  a.code_bias = code_bias;
-  a.code_index = code_index;
-  a.n_codes = n_codes;
-  a.pts = pts;
-  a.ro = ro;
-  a.rd = rd;
-  a.z = z;
-  a.n_rays = n_rays;
-  a.n_samples = n_samples;
-  a.chunk_rows = chunk_rows;
-  a.m = n_rays * n_samples;
-  CN_CHECK_ARG(cn::ceil_div(a.m, kTile) <= 0x7fffffff);
-  for (int i = 0; i < 10; ++i) a.fx[i] = freqs_xyz[i];
-  for (int i = 0; i < 4; ++i) a.fd[i] = freqs_dir[i];
-  a.raw = raw;
-  CN_CHECK_ARG(cn::aligned16(raw));  // float4 rows (include/codenerf.h)
-  a.save = save;
-  a.masks = masks;
-  // fp32: the encoding plane follows the five activation planes (cn_field_train_saved_floats)
-  if (fmt == CN_FMT_F32_W16) a.xenc = save + 5 * a.m * 256;
-  return fmt == CN_FMT_BF16X3 ? launch_field_x3(pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream))
-                              : launch_field_w16(pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream));
-}
-
-extern "C" int64_t cn_field_train_saved_floats(int fmt, int64_t m) {
-  if (m <= 0 || !(fmt == CN_FMT_F32_W16 || fmt == CN_FMT_BF16X3)) return -1;
-  // five (m, 256) activation planes; fp32: then the (m, 64) encoding plane; a 256-float scratch row
-  return 5 * m * 256 + (fmt == CN_FMT_F32_W16 ? 64 * m : 0) + 256;
-}
-
-extern "C" int cn_field_backward_x3(const float* packed_t, const uint32_t* masks, const float* d_raw,
-                                    const float* pts, const float* ro, const float* rd, const float* z,
-                                    int64_t n_rays, int64_t n_samples, int64_t chunk_rows,
-                                    const int64_t* code_index, int64_t n_codes, const float* freqs_xyz,
-                                    const float* freqs_dir, float* g_code, float* d_pts, float* d_ro, float* d_rd,
-                                    cn_stream_t stream) {
-  return cn_field_backward_fused(CN_FMT_BF16X3_T, packed_t, masks, d_raw, pts, ro, rd, z, n_rays, n_samples,
-                                 chunk_rows, code_index, n_codes, freqs_xyz, freqs_dir, g_code, d_pts, d_ro, d_rd,
-                                 stream);
-}
-
-namespace cn {
-namespace mlp {
-// cn_field_backward_fused's checks and kernel arguments (shared with cn_field_backward_fused_ws).
-int fused_backward_args(int fmt_t, const float* packed_t, const uint32_t* masks, const float* d_raw,
-                        const float* pts, const float* ro, const float* rd, const float* z, int64_t n_rays,
-                        int64_t n_samples, int64_t chunk_rows, const int64_t* code_index, int64_t n_codes,
-                        const float* freqs_xyz, const float* freqs_dir, float* g_code, float* d_pts, float* d_ro,
-                        float* d_rd, FieldArgs& a) {
-  CN_CHECK_ARG(fmt_t == CN_FMT_BF16X3_T || fmt_t == CN_FMT_F32_W16_T);
-  CN_CHECK_ARG(packed_t && masks && d_raw && rd && g_code && freqs_xyz && freqs_dir);
-  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && chunk_rows > 0 && n_codes > 0);
-  CN_CHECK_ARG(pts || (ro && z));
-  CN_CHECK_ARG(!d_pts || pts);
-  CN_CHECK_ARG(!d_ro || (ro && z && !pts));
-  CN_CHECK_ARG(code_index || n_codes == 1 || n_codes == n_rays);
-  // one code row per wave (32 samples x3, 16 samples w16): a single code, or every wave inside one ray
-  const int wave_samples = fmt_t == CN_FMT_BF16X3_T ? 32 : 16;
-  if (!(n_codes == 1 || n_samples % wave_samples == 0)) return CN_EUNSUPPORTED;
-  a = FieldArgs{};
-  a.packed = packed_t;
-  a.code_index = code_index;
-  a.n_codes = n_codes;
-  a.pts = pts;
-  a.ro = ro;
-  a.rd = rd;
-  a.z = z;
-  a.n_rays = n_rays;
-  a.n_samples = n_samples;
-  a.chunk_rows = chunk_rows;
-  a.m = n_rays * n_samples;
-  CN_CHECK_ARG(cn::ceil_div(a.m, kTile) <= 0x7fffffff);
-  for (int i = 0; i < 10; ++i) a.fx[i] = freqs_xyz[i];
-  for (int i = 0; i < 4; ++i) a.fd[i] = freqs_dir[i];
-  a.masks = const_cast<uint32_t*>(masks);
-  a.d_raw = d_raw;
-  CN_CHECK_ARG(cn::aligned16(d_raw));  // float4 rows (include/codenerf.h)
-  a.g_code = g_code;
-  a.d_pts = d_pts;
-  a.d_ro = d_ro;
-  a.d_rd = d_rd;
-  return CN_OK;
-}
 }  // namespace mlp
 }  // namespace cn
-
-extern "C" int cn_field_backward_fused(int fmt_t, const float* packed_t, const uint32_t* masks, const float* d_raw,
-                                       const float* pts, const float* ro, const float* rd, const float* z,
-                                       int64_t n_rays, int64_t n_samples, int64_t chunk_rows,
-                                       const int64_t* code_index, int64_t n_codes, const float* freqs_xyz,
-                                       const float* freqs_dir, float* g_code, float* d_pts, float* d_ro,
-                                       float* d_rd, cn_stream_t stream) {
-  FieldArgs a;
-  const int rc = fused_backward_args(fmt_t, packed_t, masks, d_raw, pts, ro, rd, z, n_rays, n_samples, chunk_rows,
-                                     code_index, n_codes, freqs_xyz, freqs_dir, g_code, d_pts, d_ro, d_rd, a);
-  if (rc != CN_OK) return rc;
-  return fmt_t == CN_FMT_BF16X3_T ? launch_field_x3_bwd(pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream))
-                                  : launch_field_w16_bwd(pts ? kFromPts : kFromRayZ, a, cn::as_stream(stream));
-}

@@ -340,12 +340,42 @@ int launch_field_prepare_w16(const PrepareModel* models, int n_models, const flo
                              int64_t n_codes, hipStream_t st);
 int launch_field_w16_bwd(int mode, FieldArgs& a, hipStream_t st);
 int launch_field_w16_bwd2(int mode, FieldArgs& a0, FieldArgs& a1, hipStream_t st);
-// cn_field_backward_fused's argument checks, into a (mlp.hip).
-int fused_backward_args(int fmt_t, const float* packed_t, const uint32_t* masks, const float* d_raw,
-                        const float* pts, const float* ro, const float* rd, const float* z, int64_t n_rays,
-                        int64_t n_samples, int64_t chunk_rows, const int64_t* code_index, int64_t n_codes,
-                        const float* freqs_xyz, const float* freqs_dir, float* g_code, float* d_pts, float* d_ro,
-                        float* d_rd, FieldArgs& a);
+
+// fp32 32x32x2 one-wave-per-SIMD variant (mlp.hip): its pack, the per-code bias rows every variant reads,
+// the forward (a.save: also the activation planes).
+int launch_pack_v1(const Params& P, float* packed, hipStream_t st);
+int launch_code_bias(const Params& P, const float* z_s, const float* z_t, int64_t n_codes, float* out, hipStream_t st);
+int launch_field_v1(int mode, FieldArgs& a, hipStream_t st);
+
+// What every field entry point receives (host side, field_api.hip): the geometry -- points, or rays and
+// depths -- the code rows' selection and the two frequency tables (host arrays of 10 and 4).
+struct FieldInputs {
+  const float* pts;
+  const float* ro;
+  const float* rd;
+  const float* z;
+  int64_t n_rays, n_samples, chunk_rows;
+  const int64_t* code_index;
+  int64_t n_codes;
+  const float* freqs_xyz;
+  const float* freqs_dir;
+  const float* x;  // kDensityForm only: encoded rows as a third geometry (n_rays rows, n_samples 1)
+};
+enum FieldForm {
+  kRayForm = 0,  // rd required, pts or (ro, z); chunk_rows; both frequency tables
+  // the density entries: exactly one of pts, (ro, rd, z) and x; chunk_rows = n_rays; no freqs_dir
+  kDensityForm = 1,
+  kEncodeForm = 2,  // cn_encode_inputs: kRayForm without codes and without the tile bound
+};
+// The one place a field entry point's inputs are checked: `in` under `form` (CN_EINVAL; n_rays * n_samples
+// must not overflow), then, wave_samples != 0, the fused backwards' one code row per wave_samples-sample
+// wave (CN_EUNSUPPORTED), then the tile bound (CN_EINVAL).  On CN_OK `a` is zeroed and holds the inputs
+// (m = n_rays * n_samples); the caller adds its own buffers.
+int field_args(const FieldInputs& in, FieldForm form, int wave_samples, FieldArgs& a);
+// The same for the encoded-rows entries (cn_mlp_forward*): x (m, 90), one code row, one per row or code_index.
+int encoded_args(const float* x, int64_t m, const int64_t* code_index, int64_t n_codes, FieldArgs& a);
+// cn_field_backward_fused's checks and kernel arguments (f.workspace is the caller's).
+int fused_backward_args(int fmt_t, const cn_field_fused_bwd& f, FieldArgs& a);
 
 // 3xbf16 16x16x32 two-waves-per-SIMD variant (mlp_x3w.hip): inference forward only.
 int64_t packed_floats_x3w();
