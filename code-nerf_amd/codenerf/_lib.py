@@ -34,6 +34,7 @@ def kernel_format(precision: str) -> str:
     return precision
 CN_CODE_BIAS_STRIDE = 520
 CN_EMPTY_SIGMA_RAW = -1.0e4     # sigma_raw of a culled slot (cn_occupancy_expand): exactly zero density
+CN_MAX_SCENE_OBJECTS = 8        # objects of one cn_volume_render_compose / cn_object_rays call
 
 _p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -117,6 +118,8 @@ SIGNATURES = {
     "cn_occupancy_expand": (_i, [_p, _p, _i64, _i64, _p, _p]),
     "cn_weight_cull": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _f, ctypes.c_double, _p, _p, _p, _p, _p, _p, _p]),
     "cn_scatter_rgb": (_i, [_p, _p, _i64, _p, _i64, _p]),
+    "cn_volume_render_compose": (_i, [ctypes.POINTER(_p), _i, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    "cn_object_rays": (_i, [_p, _p, _i64, _fp, _i, _p, _p, _p]),
     "cn_isosurface_workspace_bytes": (_i64, [_i64]),
     "cn_isosurface_count": (_i, [_p, _i64, _f, _p, _p, _p]),
     "cn_isosurface_emit": (_i, [_p, _p, _i64, _f, _p, _i64, _i64, _p, _p, _p]),

@@ -26,7 +26,7 @@ from .volumetric_render import volume_render
 __all__ = ["RaySampler", "PointSampler", "PositionalEmbedder", "volume_render", "prepare_samplers",
            "prepare_embedders", "predict_radiance_and_render", "forward_pass", "parallel_image_render",
            "render_rays", "gather_rows", "gather_views", "density", "density_grid", "OccupancyGrid", "Mesh", "extract_mesh",
-           "density_gradient", "normals"]
+           "density_gradient", "normals", "SceneObject", "render_scene"]
 
 
 def prepare_samplers(cfg, height: int, width: int, intrinsics, datatype, device) -> Tuple[RaySampler, PointSampler]:
@@ -605,6 +605,102 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
         with torch.no_grad():
             gs = _density_gradient_rows(fine_model, embedders, cs, code_index, ro=ro.detach(), rd=rd.detach(), z=z_f)
             out["normal_fine"] = _composite_normals(w_f, _normals_from_gradient(gs[..., :3]))
+    return out
+
+
+class SceneObject:
+    """One instance in a scene (render_scene): its codes ``z_s`` / ``z_t`` (one row each), its
+    OccupancyGrid in the object's own frame, and its rigid pose, the object-to-world ``rotation`` (3, 3) and
+    ``translation`` (3,) -- host values (nested sequences or CPU tensors), the identity by default.
+    The grid is mandatory (``OccupancyGrid.full`` is the minimum): a field means nothing outside the region
+    it was trained on and contributes exactly nothing there.  Uniform scale is not a pose: it would
+    rescale the densities.  ``coarse_model`` / ``fine_model``: this object's category models, the
+    scene's by default."""
+
+    def __init__(self, z_s: torch.Tensor, z_t: torch.Tensor, occupancy: OccupancyGrid, rotation=None, translation=None,
+                 coarse_model=None, fine_model=None):
+        if not isinstance(occupancy, OccupancyGrid):
+            raise ValueError("a scene object needs its OccupancyGrid (OccupancyGrid.full(...) at the least): it "
+                             "bounds the region the object's field is evaluated in")
+        rot = [[float(v) for v in row] for row in ([[1, 0, 0], [0, 1, 0], [0, 0, 1]] if rotation is None else rotation)]
+        t = [float(v) for v in ((0, 0, 0) if translation is None else translation)]
+        if len(rot) != 3 or any(len(row) != 3 for row in rot) or len(t) != 3:
+            raise ValueError("rotation must be (3, 3) and translation (3,)")
+        flat = [v for row in rot for v in row] + t
+        if any(v != v or v in (float("inf"), float("-inf")) for v in flat):
+            raise ValueError("rotation and translation must be finite")
+        gram = max(abs(sum(rot[k][i] * rot[k][j] for k in range(3)) - (1.0 if i == j else 0.0))
+                   for i in range(3) for j in range(3))
+        if gram > 1e-5:
+            raise ValueError(f"rotation must be orthonormal (max |R^T R - I| = {gram:.3g} > 1e-5): a scene pose is "
+                             "rigid, scale would rescale the densities")
+        for name, code in (("z_s", z_s), ("z_t", z_t)):
+            if code.dim() != 2 or (code.shape[0] != 1 and code.stride(0) != 0):
+                raise ValueError(f"{name} must be one code row (1, C) (or an expand() of one)")
+        self.codes = (z_s, z_t)                     # as given: what render_scene's gradient check looks at
+        self.z_s, self.z_t = (c if c.shape[0] == 1 else c[:1] for c in self.codes)
+        self.occupancy, self.rotation, self.translation = occupancy, rot, t
+        self.coarse_model, self.fine_model = coarse_model, fine_model
+
+
+def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: PointSampler, embedders, coarse_model,
+                 fine_model=None, *, coarse_only: bool = False, coarse_rgb: bool = True,
+                 t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Several posed objects (1..8 SceneObjects) in one image: render_rays' hierarchical render of the world
+    rays ``ro`` / ``rd`` (R, 3), with the objects composed per sample.  A rigid pose keeps the ray
+    parameter, so one set of depths along the world ray serves every object: the coarse depths
+    (ops.sample_uniform), each object's field on its own object-frame rays (ops.object_rays) under its grid
+    (the density kernel when ``coarse_rgb=False``), ops.volume_render_compose with the world ``rd``,
+    ops.sample_pdf on the composed weights, the objects' fine fields at the shared fine depths and the
+    composition again.  Interpenetrating objects and partial transmittance are integrated as one medium
+    (include/codenerf.h's rule), not blended per image.
+    Returns render_rays' entries plus "acc_objects_coarse" / "acc_objects_fine" (K, R): each object's share
+    of "acc_*", its instance mask.  A sample's view direction is its own ray's (``chunk_rows`` is the whole
+    ray list).  With one identity-posed object every shared entry is bitwise
+    render_rays(..., occupancy=grid, chunk_rows=None)'s.
+    Inference only.  Each object's kept count is read back once per field call -- 2 K host
+    synchronisations per render (K with ``coarse_only``) -- so this render is not graph-capturable."""
+    objects = list(objects)
+    if not 1 <= len(objects) <= 8 or not all(isinstance(o, SceneObject) for o in objects):
+        raise ValueError(f"a scene holds 1..8 SceneObjects, got {len(objects)} entries")
+    coarse_models = [o.coarse_model if o.coarse_model is not None else coarse_model for o in objects]
+    fine_models = [o.fine_model if o.fine_model is not None else fine_model for o in objects]
+    if not coarse_only and any(m is None for m in fine_models):
+        raise ValueError("every object needs a fine model (its own or the scene's) unless coarse_only=True")
+    if torch.is_grad_enabled() and (
+            any(t is not None and t.requires_grad for t in [ro, rd] + [c for o in objects for c in o.codes]) or
+            any(p.requires_grad for m in coarse_models + ([] if coarse_only else fine_models)
+                for p in _unwrap(m).param_list())):
+        raise ValueError("render_scene is an inference render: the compacted fields and the composition have no "
+                         "backward (render under torch.no_grad())")
+    n = ro.shape[0]
+    ps = point_sampler
+    with torch.no_grad():
+        if ps.perturb and t_rand is None:
+            t_rand = torch.rand(n, ps.num_samples_coarse, dtype=torch.float32, device=ro.device)
+        _, z_c = ops.sample_uniform(ro, rd, ps.z_vals, ps.lower, ps.upper, t_rand if ps.perturb else None,
+                                    want_pts=False)
+        ro_k, rd_k = ops.object_rays(ro, rd, [(o.rotation, o.translation) for o in objects])
+
+        def fields(models, z, density_only):
+            return [_culled_field(m, embedders, rd_k[k], o.z_s, o.z_t, n, ro_k[k], z, o.occupancy, density_only)
+                    for k, (o, m) in enumerate(zip(objects, models))]
+
+        rgb_c, disp_c, acc_c, w_c, depth_c, obj_c = ops.volume_render_compose(fields(coarse_models, z_c, not coarse_rgb),
+                                                                             z_c, rd)
+        out = {"rgb_coarse": rgb_c, "disp_coarse": disp_c, "acc_coarse": acc_c, "weights_coarse": w_c,
+               "depth_coarse": depth_c, "z_coarse": z_c, "acc_objects_coarse": obj_c}
+        if not coarse_rgb:
+            del out["rgb_coarse"]       # composited from zero colours: not a result
+        if coarse_only:
+            return out
+        if ps.perturb and u is None:
+            u = torch.rand(n, ps.num_samples_fine, dtype=torch.float32, device=ro.device)
+        _, z_f = ops.sample_pdf(ro, rd, w_c[..., 1:-1], z_c, ps.num_samples_fine, u if ps.perturb else ps.u_lin,
+                                want_pts=False)
+        rgb_f, disp_f, acc_f, _, depth_f, obj_f = ops.volume_render_compose(fields(fine_models, z_f, False), z_f, rd)
+        out.update({"rgb_fine": rgb_f, "disp_fine": disp_f, "acc_fine": acc_f, "depth_fine": depth_f, "z_fine": z_f,
+                    "acc_objects_fine": obj_f})
     return out
 
 

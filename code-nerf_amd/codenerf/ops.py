@@ -340,6 +340,64 @@ def volume_render(raw: Tensor, z: Tensor, rd: Tensor, want_weights: bool = True)
     return rgb, disp, acc, w, depth
 
 
+def volume_render_compose(raws: Sequence[Tensor], z: Tensor, rd: Tensor, want_weights: bool = True,
+                          want_acc_objects: bool = True):
+    """Several objects' raw rows at the same depths as one ray integral (cn_volume_render_compose; the rule
+    is in include/codenerf.h): ``raws`` 1..8 tensors (R, S, 4), ``z`` (R, S), the world ``rd`` (R, 3) ->
+    rgb, disp, acc, weights, depth as volume_render, and acc_objects (K, R): each object's share of acc, its
+    instance mask.  One object gives volume_render's bits."""
+    lib = _lib_ready()
+    raws = list(raws)
+    assert 1 <= len(raws) <= _lib.CN_MAX_SCENE_OBJECTS, \
+        f"a scene holds 1..{_lib.CN_MAX_SCENE_OBJECTS} objects, got {len(raws)}"
+    z, rd = _aligned16(_cuda(z, "depth_values")), _cuda(rd, "ray_directions")
+    n, s = z.shape
+    raws = [_aligned16(_cuda(raw, f"raws[{k}]")) for k, raw in enumerate(raws)]
+    for raw in raws:
+        assert raw.shape == (n, s, 4), "every radiance field must be (num_rays, num_samples, 4)"
+    assert rd.shape == (n, 3), "ray_directions must be (num_rays, 3)"
+    dev = z.device
+    rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    disp = torch.empty(n, device=dev, dtype=torch.float32)
+    acc = torch.empty_like(disp)
+    depth = torch.empty_like(disp)
+    w = torch.empty(n, s, device=dev, dtype=torch.float32) if want_weights else None
+    acc_objects = torch.empty(len(raws), n, device=dev, dtype=torch.float32) if want_acc_objects else None
+    if n:
+        pointers, keep = _lib.pointer_array(raws)
+        check(lib.cn_volume_render_compose(pointers, len(raws), ptr(z), ptr(rd), n, s, ptr(rgb), ptr(disp), ptr(acc),
+                                           ptr(w), ptr(depth), ptr(acc_objects), stream_of(z)),
+              "cn_volume_render_compose")
+        del keep
+    if w is not None and s == 1:
+        w = w[:, :0]          # as volume_render: the reference's S == 1 weights are (R, 0)
+    return rgb, disp, acc, w, depth, acc_objects
+
+
+def object_rays(ro: Tensor, rd: Tensor, poses) -> Tuple[Tensor, Tensor]:
+    """World rays (R, 3) in the frames of K posed objects (cn_object_rays) -> ro (K, R, 3), rd (K, R, 3).
+    ``poses``: K host (rotation (3, 3) row-major object-to-world, translation (3,)) pairs of floats; the
+    ray parameter is unchanged, so ro[k] + z rd[k] is the world point ro + z rd in object k's frame."""
+    lib = _lib_ready()
+    ro, rd = _cuda(ro, "ro"), _cuda(rd, "rd")
+    n = ro.shape[0]
+    assert ro.shape == (n, 3) and rd.shape == (n, 3), "ro / rd must be (num_rays, 3)"
+    poses = list(poses)
+    assert 1 <= len(poses) <= _lib.CN_MAX_SCENE_OBJECTS, \
+        f"a scene holds 1..{_lib.CN_MAX_SCENE_OBJECTS} objects, got {len(poses)}"
+    flat = []
+    for rot, t in poses:
+        rows = [float(v) for row in rot for v in row] + [float(v) for v in t]
+        assert len(rows) == 12, "a pose is a (3, 3) rotation and a (3,) translation"
+        flat += rows
+    ro_out = torch.empty(len(poses), n, 3, device=ro.device, dtype=torch.float32)
+    rd_out = torch.empty(len(poses), n, 3, device=ro.device, dtype=torch.float32)
+    if n:
+        check(lib.cn_object_rays(ptr(ro), ptr(rd), n, _lib.host_floats(flat), len(poses), ptr(ro_out), ptr(rd_out),
+                                 stream_of(ro)), "cn_object_rays")
+    return ro_out, rd_out
+
+
 # ------------------------------------------------------------------ MLP
 
 

@@ -96,6 +96,55 @@ extern "C" int cn_gather_rays(const float* ro, const float* rd, int64_t batch, i
   return cn::launch_status();
 }
 
+// ---------------------------------------------------------------- scene objects
+namespace {
+
+struct ObjectPoses {
+  float p[CN_MAX_SCENE_OBJECTS][12];  // R row-major (object to world), then t
+};
+
+// World rays in every object's frame: the inverse rigid map R^T (x - t), every operation rounded
+// (include/codenerf.h).  One lane per ray, the object is the block's y index.
+__global__ __launch_bounds__(256) void object_rays_kernel(const float* __restrict__ ro, const float* __restrict__ rd,
+                                                          int64_t n_rays, ObjectPoses poses,
+                                                          float* __restrict__ ro_out, float* __restrict__ rd_out) {
+  const int k = blockIdx.y;
+  float m[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) m[e] = poses.p[k][e];
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n_rays; r += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t q = k * n_rays + r;
+    const float d0 = __fsub_rn(ro[3 * r], m[9]), d1 = __fsub_rn(ro[3 * r + 1], m[10]);
+    const float d2 = __fsub_rn(ro[3 * r + 2], m[11]);
+    const float v0 = rd[3 * r], v1 = rd[3 * r + 1], v2 = rd[3 * r + 2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      ro_out[3 * q + i] =
+          __fadd_rn(__fadd_rn(__fmul_rn(d0, m[i]), __fmul_rn(d1, m[3 + i])), __fmul_rn(d2, m[6 + i]));
+      rd_out[3 * q + i] =
+          __fadd_rn(__fadd_rn(__fmul_rn(v0, m[i]), __fmul_rn(v1, m[3 + i])), __fmul_rn(v2, m[6 + i]));
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int cn_object_rays(const float* ro, const float* rd, int64_t n_rays, const float* poses, int n_objects,
+                              float* ro_out, float* rd_out, cn_stream_t stream) {
+  CN_CHECK_ARG(ro && rd && poses && ro_out && rd_out && n_rays > 0);
+  CN_CHECK_ARG(n_objects >= 1 && n_objects <= CN_MAX_SCENE_OBJECTS);
+  ObjectPoses p = {};
+  for (int k = 0; k < n_objects; ++k)
+    for (int e = 0; e < 12; ++e) {
+      const float v = poses[12 * k + e];
+      CN_CHECK_ARG(v - v == 0.0f);  // finite
+      p.p[k][e] = v;
+    }
+  hipLaunchKernelGGL(object_rays_kernel, dim3(cn::elementwise_grid(n_rays, 256), n_objects), dim3(256), 0,
+                     cn::as_stream(stream), ro, rd, n_rays, p, ro_out, rd_out);
+  return cn::launch_status();
+}
+
 // ---------------------------------------------------------------- backward
 namespace {
 

@@ -195,6 +195,46 @@ __device__ __forceinline__ void load_raw_lds(const float4* sl, int q0, int j0, i
   for (int i = 0; i < K; ++i) rv[i] = (i < run && j0 + i < S_in) ? sl[pad4(q0 + i)] : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+// A raw row's density and colour channel (volumetric_render.py:32 and :28), shared by the plain and the
+// composed render: shifted_softplus(x) = softplus(x - 1); widened_sigmoid(x) = sigmoid(x) * 1.002 - 0.001.
+__device__ __forceinline__ float raw_sigma(float x) { return cn::softplus20(__fsub_rn(x, 1.0f)); }
+__device__ __forceinline__ float raw_colour(float x) {
+  return __fsub_rn(__fmul_rn(cn::sigmoid_hw(x), 1.002f), 0.001f);
+}
+
+// This lane's run of weights: 16-B stores where the run is aligned (see load_depths).  S: the samples
+// that contribute (0 for the sample-free S_in == 1).
+template <int K>
+__device__ __forceinline__ void store_run_weights(float* __restrict__ weights, int64_t r, int j0, int run, int S_in,
+                                                  int S, const float (&wv)[K]) {
+  float* wr = weights + r * S_in;
+  if (K % 4 == 0 && run % 4 == 0 && (S_in & 3) == 0 && j0 + run <= S_in && S > 0) {
+#pragma unroll
+    for (int q = 0; q < K / 4; ++q)
+      if (4 * q < run)
+        nt_store4(make_float4(wv[4 * q], wv[4 * q + 1], wv[4 * q + 2], wv[4 * q + 3]),
+                                    reinterpret_cast<float4*>(wr + j0) + q);
+  } else {
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+      if (i < run && j0 + i < S) wr[j0 + i] = wv[i];
+  }
+}
+
+// The ray's maps from its summed colour, depth and opacity (the lane that holds the sums stores).
+__device__ __forceinline__ void store_ray_maps(int64_t r, float cr, float cg, float cb, float dep, float ac,
+                                               float* __restrict__ rgb, float* __restrict__ disp,
+                                               float* __restrict__ acc, float* __restrict__ depth) {
+  rgb[3 * r] = cr;
+  rgb[3 * r + 1] = cg;
+  rgb[3 * r + 2] = cb;
+  depth[r] = dep;
+  acc[r] = ac;
+  // (:63) torch.max propagates NaN: disp is NaN when acc == 0
+  const float q = dep / ac;
+  disp[r] = (q != q) ? q : 1.0f / fmaxf(1e-10f, q);
+}
+
 // One lane's part of a ray (lane sub of its L): the run's depths zz and raw rows rv loaded, |rd| = nrm.
 template <int K, bool FULL, int L>
 __device__ __forceinline__ void render_run(const float (&zz)[K], const float4 (&rv)[K], int S_in, int64_t r, float nrm,
@@ -219,7 +259,7 @@ __device__ __forceinline__ void render_run(const float (&zz)[K], const float4 (&
       // dists = [z[1:] - z[:-1], 1e10] (:41-44), delta = dists * |rd| (:45)
       const float zn = (i + 1 < run) ? zz[(i + 1) % K] : znext;
       const float dist = (j + 1 < S) ? __fsub_rn(zn, zz[i]) : 1e10f;
-      const float sigma = cn::softplus20(__fsub_rn(rv[i].w, 1.0f));  // shifted_softplus (:32)
+      const float sigma = raw_sigma(rv[i].w);  // shifted_softplus (:32)
       sd[i] = __fmul_rn(sigma, __fmul_rn(dist, nrm));
       if (j + 1 < S) run_sum += static_cast<double>(sd[i]);
     }
@@ -236,9 +276,7 @@ __device__ __forceinline__ void render_run(const float (&zz)[K], const float4 (&
       const float alpha = __fsub_rn(1.0f, expf(-sd[i]));           // (:58)
       const float w = __fmul_rn(alpha, trans);                     // (:59)
       // widened_sigmoid (:28): sigmoid(x) * 1.002 - 0.001
-      const float c0 = __fsub_rn(__fmul_rn(cn::sigmoid_hw(rv[i].x), 1.002f), 0.001f);
-      const float c1 = __fsub_rn(__fmul_rn(cn::sigmoid_hw(rv[i].y), 1.002f), 0.001f);
-      const float c2 = __fsub_rn(__fmul_rn(cn::sigmoid_hw(rv[i].z), 1.002f), 0.001f);
+      const float c0 = raw_colour(rv[i].x), c1 = raw_colour(rv[i].y), c2 = raw_colour(rv[i].z);
       cr += w * c0;
       cg += w * c1;
       cb += w * c2;
@@ -248,35 +286,13 @@ __device__ __forceinline__ void render_run(const float (&zz)[K], const float4 (&
       if (j + 1 < S) prefix += static_cast<double>(sd[i]);
     }
   }
-  if (weights) {  // this lane's run of weights: 16-B stores where the run is aligned (see load_depths)
-    float* wr = weights + r * S_in;
-    if (K % 4 == 0 && run % 4 == 0 && (S_in & 3) == 0 && j0 + run <= S_in && S > 0) {
-#pragma unroll
-      for (int q = 0; q < K / 4; ++q)
-        if (4 * q < run)
-          nt_store4(make_float4(wv[4 * q], wv[4 * q + 1], wv[4 * q + 2], wv[4 * q + 3]),
-                                      reinterpret_cast<float4*>(wr + j0) + q);
-    } else {
-#pragma unroll
-      for (int i = 0; i < K; ++i)
-        if (i < run && j0 + i < S) wr[j0 + i] = wv[i];
-    }
-  }
+  if (weights) store_run_weights<K>(weights, r, j0, run, S_in, S, wv);
   cr = ray_sum<L>(cr);
   cg = ray_sum<L>(cg);
   cb = ray_sum<L>(cb);
   dep = ray_sum<L>(dep);
   ac = ray_sum<L>(ac);
-  if (sub == (L == 16 ? 15 : 63)) {
-    rgb[3 * r] = cr;
-    rgb[3 * r + 1] = cg;
-    rgb[3 * r + 2] = cb;
-    depth[r] = dep;
-    acc[r] = ac;
-    // (:63) torch.max propagates NaN: disp is NaN when acc == 0
-    const float q = dep / ac;
-    disp[r] = (q != q) ? q : 1.0f / fmaxf(1e-10f, q);
-  }
+  if (sub == (L == 16 ? 15 : 63)) store_ray_maps(r, cr, cg, cb, dep, ac, rgb, disp, acc, depth);
 }
 
 template <int K, bool FULL, int L>
@@ -391,6 +407,198 @@ extern "C" int cn_volume_render(const float* raw, const float* z, const float* r
   }
   CN_VOLUME_DISPATCH(volume_render_kernel, n_samples, n_rays, cn::as_stream(stream), raw, z, rd, n_rays,
                      static_cast<int>(n_samples), rgb, disp, acc, weights, depth);
+  return cn::launch_status();
+}
+
+// ---------------------------------------------------------------- scene composition
+// cn_volume_render_compose: the raw rows of n_objects objects at the same depths become one ray integral
+// (the rule is in include/codenerf.h).  volume_render_kernel's geometry -- L lanes per ray, a run of
+// <= K samples per lane, the wave's rows staged through LDS -- with each object's rows staged in turn
+// through the same LDS block.  Per sample a lane keeps the summed density, the colour numerator, the
+// count of active objects and the last active object's colour (the mix's three cases), and every
+// object's own density for the shares: NOBJ * K <= 64 values.  NOBJ bounds n_objects at compile time, so
+// every array is indexed statically and stays in registers.
+// Algorithmic bytes per ray: 12 (rd) + (16 n_objects + 4) S in, 4 S + 20 + 4 n_objects out.
+namespace {
+
+struct ComposeRaws {
+  const float* p[CN_MAX_SCENE_OBJECTS];
+};
+
+template <int K, int L, int NOBJ>
+__global__ __launch_bounds__(256) void volume_render_compose_kernel(
+    ComposeRaws raws, int n_objects, const float* __restrict__ z, const float* __restrict__ rd, int64_t n_rays,
+    int S_in, float* __restrict__ rgb, float* __restrict__ disp, float* __restrict__ acc,
+    float* __restrict__ weights, float* __restrict__ depth, float* __restrict__ acc_objects) {
+  static_assert(K <= kMaxRun && (L == 16 || L == 64) && NOBJ >= 1 && NOBJ <= CN_MAX_SCENE_OBJECTS, "instance");
+  __shared__ float4 slds[4 * 80 * K];  // per wave: one object's <= 64 K quads, padded 5 / 4
+  const int sub = threadIdx.x & (L - 1), lane = threadIdx.x & 63;
+  const int64_t r = ((int64_t)blockIdx.x * 256 + threadIdx.x) / L;
+  const int64_t rw0 = r - lane / L;  // the wave's first ray
+  if (rw0 >= n_rays) return;         // the whole wave
+  const int nq = static_cast<int>(min<int64_t>(64 / L, n_rays - rw0)) * S_in;  // the wave's valid quads
+  float4* sl = slds + (threadIdx.x >> 6) * 80 * K;
+  // a ray past n_rays (L = 16 only) copies its share of every object's rows, accumulates nothing and
+  // leaves before the cross-lane steps, with its whole row
+  const bool live = r < n_rays;
+  const int S = S_in == 1 ? 0 : S_in;  // see render_run: S == 1 has no contributing sample
+  const int run = (S_in + L - 1) / L;
+  const int j0 = sub * run;
+  const int q0 = (lane / L) * S_in + j0;  // this run's first quad in the wave block
+  float zz[K];
+  float nrm = 0.0f;
+  if (live) {
+    load_depths<K>(z + r * S_in, j0, run, S_in, zz);
+    const float d0 = rd[3 * r], d1 = rd[3 * r + 1], d2 = rd[3 * r + 2];
+    nrm = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+  }
+
+  float sig[K], num[K][3], lone[K][3], sk[NOBJ][K];
+  int cnt[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    sig[i] = 0.0f;
+    cnt[i] = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) num[i][c] = lone[i][c] = 0.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < NOBJ; ++k) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) sk[k][i] = 0.0f;
+    if (k >= n_objects) continue;  // uniform
+    // the previous object's LDS reads stay ahead of these stores, and these stores ahead of the reads
+    // (no instruction: the LDS operations of one wave execute in program order)
+    __builtin_amdgcn_wave_barrier();
+    stage_rows_in<K>(reinterpret_cast<const float4*>(raws.p[k]) + rw0 * S_in, nq, sl, lane);
+    __builtin_amdgcn_wave_barrier();
+    if (!live) continue;
+    float4 rv[K];
+    load_raw_lds<K>(sl, q0, j0, run, S_in, rv);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      if (i < run && j0 + i < S) {
+        const float s = raw_sigma(rv[i].w);
+        sk[k][i] = s;
+        sig[i] = __fadd_rn(sig[i], s);
+        if (s != 0.0f) {  // active (a NaN density is)
+          const float c0 = raw_colour(rv[i].x), c1 = raw_colour(rv[i].y), c2 = raw_colour(rv[i].z);
+          cnt[i] += 1;
+          lone[i][0] = c0;
+          lone[i][1] = c1;
+          lone[i][2] = c2;
+          num[i][0] = __fadd_rn(num[i][0], __fmul_rn(s, c0));
+          num[i][1] = __fadd_rn(num[i][1], __fmul_rn(s, c1));
+          num[i][2] = __fadd_rn(num[i][2], __fmul_rn(s, c2));
+        }
+      }
+    }
+  }
+  if (!live) return;  // whole rays leave together: the cross-lane steps never read an exited lane
+
+  // from here render_run's arithmetic on the summed density and the mixed colour
+  float sd[K], wv[K];
+  const float znext = next_lane<L>(zz[0]);
+  double run_sum = 0.0;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const int j = j0 + i;
+    sd[i] = 0.0f;
+    if (i < run && j < S) {
+      const float zn = (i + 1 < run) ? zz[(i + 1) % K] : znext;
+      const float dist = (j + 1 < S) ? __fsub_rn(zn, zz[i]) : 1e10f;
+      sd[i] = __fmul_rn(sig[i], __fmul_rn(dist, nrm));
+      if (j + 1 < S) run_sum += static_cast<double>(sd[i]);
+    }
+  }
+  double prefix = ray_exclusive_scan<L>(run_sum);
+
+  float cr = 0.f, cg = 0.f, cb = 0.f, dep = 0.f, ac = 0.f, ao[NOBJ];
+#pragma unroll
+  for (int k = 0; k < NOBJ; ++k) ao[k] = 0.0f;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const int j = j0 + i;
+    wv[i] = 0.0f;
+    if (i < run && j < S) {
+      const float trans = expf(-static_cast<float>(prefix));
+      const float alpha = __fsub_rn(1.0f, expf(-sd[i]));
+      const float w = __fmul_rn(alpha, trans);
+      // no active object: no colour; one: its colour as it is; more: the density-weighted mean
+      float c0 = lone[i][0], c1 = lone[i][1], c2 = lone[i][2];
+      if (cnt[i] > 1) {
+        c0 = __fdiv_rn(num[i][0], sig[i]);
+        c1 = __fdiv_rn(num[i][1], sig[i]);
+        c2 = __fdiv_rn(num[i][2], sig[i]);
+      }
+      cr += w * c0;
+      cg += w * c1;
+      cb += w * c2;
+      dep += w * zz[i];
+      ac += w;
+      wv[i] = w;
+#pragma unroll
+      for (int k = 0; k < NOBJ; ++k) {
+        const float share = sk[k][i] != 0.0f ? (cnt[i] > 1 ? __fdiv_rn(sk[k][i], sig[i]) : 1.0f) : 0.0f;
+        ao[k] += w * share;
+      }
+      if (j + 1 < S) prefix += static_cast<double>(sd[i]);
+    }
+  }
+  if (weights) store_run_weights<K>(weights, r, j0, run, S_in, S, wv);
+  cr = ray_sum<L>(cr);
+  cg = ray_sum<L>(cg);
+  cb = ray_sum<L>(cb);
+  dep = ray_sum<L>(dep);
+  ac = ray_sum<L>(ac);
+#pragma unroll
+  for (int k = 0; k < NOBJ; ++k) ao[k] = ray_sum<L>(ao[k]);
+  if (sub == (L == 16 ? 15 : 63)) {
+    store_ray_maps(r, cr, cg, cb, dep, ac, rgb, disp, acc, depth);
+    if (acc_objects) {
+#pragma unroll
+      for (int k = 0; k < NOBJ; ++k)
+        if (k < n_objects) acc_objects[k * n_rays + r] = ao[k];
+    }
+  }
+}
+
+template <int NOBJ>
+void launch_compose(const ComposeRaws& raws, int n_objects, const float* z, const float* rd, int64_t n_rays, int S,
+                    float* rgb, float* disp, float* acc, float* weights, float* depth, float* acc_objects,
+                    hipStream_t stream) {
+  const dim3 g16(static_cast<unsigned>(cn::ceil_div(n_rays, 16))), g64(static_cast<unsigned>(cn::ceil_div(n_rays, 4)));
+#define CN_COMPOSE_LAUNCH(K, L, GRID)                                                                         \
+  hipLaunchKernelGGL((volume_render_compose_kernel<K, L, NOBJ>), GRID, dim3(256), 0, stream, raws, n_objects, z, rd, \
+                     n_rays, S, rgb, disp, acc, weights, depth, acc_objects)
+  if (S <= 64) CN_COMPOSE_LAUNCH(4, 16, g16);
+  else if (S <= 128) CN_COMPOSE_LAUNCH(8, 16, g16);
+  else if (S <= 256) CN_COMPOSE_LAUNCH(4, 64, g64);
+  else CN_COMPOSE_LAUNCH(8, 64, g64);
+#undef CN_COMPOSE_LAUNCH
+}
+
+}  // namespace
+
+extern "C" int cn_volume_render_compose(const float* const* raws, int n_objects, const float* z, const float* rd,
+                                        int64_t n_rays, int64_t n_samples, float* rgb, float* disp, float* acc,
+                                        float* weights, float* depth, float* acc_objects, cn_stream_t stream) {
+  CN_CHECK_ARG(raws && z && rd && rgb && disp && acc && depth);
+  CN_CHECK_ARG(n_objects >= 1 && n_objects <= CN_MAX_SCENE_OBJECTS);
+  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && n_samples <= kMaxSamples);
+  CN_CHECK_ARG(cn::aligned16(z) && cn::aligned16(weights));
+  ComposeRaws p = {};
+  for (int k = 0; k < n_objects; ++k) {
+    CN_CHECK_ARG(raws[k] && cn::aligned16(raws[k]));
+    p.p[k] = raws[k];
+  }
+  const int s = static_cast<int>(n_samples);
+  hipStream_t st = cn::as_stream(stream);
+  // the object count's compile-time bound: 1, 2, 4 or 8
+  if (n_objects == 1) launch_compose<1>(p, n_objects, z, rd, n_rays, s, rgb, disp, acc, weights, depth, acc_objects, st);
+  else if (n_objects == 2) launch_compose<2>(p, n_objects, z, rd, n_rays, s, rgb, disp, acc, weights, depth, acc_objects, st);
+  else if (n_objects <= 4) launch_compose<4>(p, n_objects, z, rd, n_rays, s, rgb, disp, acc, weights, depth, acc_objects, st);
+  else launch_compose<8>(p, n_objects, z, rd, n_rays, s, rgb, disp, acc, weights, depth, acc_objects, st);
   return cn::launch_status();
 }
 

@@ -471,6 +471,53 @@ int cn_weight_cull(const float* weights, const float* ro, const float* rd, const
 int cn_scatter_rgb(const float* raw_compact, const int32_t* sample_index, int64_t n_rows, float* raw,
                    int64_t n_slots, cn_stream_t stream);
 
+/* --- Scene composition (inference) --------------------------------------
+ * Several posed objects in one image.  A rigid pose keeps the ray parameter -- the world point
+ * ro + z rd is ro' + z rd' in the object's frame (cn_object_rays) -- so every object is sampled at the
+ * same depths z[r][s] along the world ray, and the K objects' raw rows of a sample become one ray
+ * integral by the rule below (cn_volume_render_compose).  Every implementation follows it.
+ * For sample (r, s) and objects k = 0 .. K-1 with raw rows raw_k[r][s] = (x0, x1, x2, xs):
+ *   sigma_k = softplus20(xs - 1) and c_k[ch] = sigmoid(x_ch) * 1.002 - 0.001, cn_volume_render's
+ *     expressions with its intrinsics;
+ *   sigma = ((0 + sigma_0) + sigma_1) + ..., fp32, ascending k;
+ *   object k is ACTIVE at the sample iff sigma_k != 0 (a NaN density is active);
+ *   colour c, by the number of active objects: none (0, 0, 0); exactly one (object a) c_a as it is;
+ *     two or more c[ch] = (sum_k sigma_k c_k[ch]) / sigma over the active k, ascending, from 0, every
+ *     product, sum and the division rounded in fp32 (an inactive object's row contributes nothing,
+ *     whatever its colours hold);
+ *   share_k: 0 for an inactive object, 1 for the only active one, else sigma_k / sigma (fp32).
+ * sigma and c then go through cn_volume_render's arithmetic unchanged: dist with the 1e10 last
+ * interval, delta = dist |rd|, the double-precision exclusive scan of sigma delta, trans, alpha and w,
+ * the per-lane runs and the order in which rgb, depth and acc are summed, disp, and the sample-free
+ * n_samples = 1 case.  acc_objects[k][r] = sum_s w_s share_k,s, summed in acc's order, is object k's
+ * instance mask.
+ * Consequences: a slot culled by cn_occupancy_expand (CN_EMPTY_SIGMA_RAW) is inactive; a ray whose
+ * every sample has at most one active object gets, bit for bit, what cn_volume_render returns for the
+ * raw tensor holding each sample's active row, whatever the order of the objects; one object is
+ * cn_volume_render. */
+#define CN_MAX_SCENE_OBJECTS 8
+
+/* The rule above.  raws: HOST array of n_objects device pointers to (n_rays, n_samples, 4) tensors;
+ * z, rd and the outputs as in cn_volume_render; weights (n_rays, n_samples) and acc_objects
+ * (n_objects, n_rays) may be NULL.  Every raws[k], z and weights 16-B aligned.  One launch on
+ * `stream`: no workspace, no atomics, no synchronisation.
+ * CN_EINVAL before any launch: a required pointer or an entry of raws NULL; n_objects outside
+ * 1..CN_MAX_SCENE_OBJECTS; n_rays <= 0; n_samples outside 1..512; a misaligned tensor. */
+int cn_volume_render_compose(const float* const* raws, int n_objects, const float* z, const float* rd,
+                             int64_t n_rays, int64_t n_samples, float* rgb, float* disp, float* acc,
+                             float* weights, float* depth, float* acc_objects, cn_stream_t stream);
+
+/* World rays (n_rays, 3) in the frame of each of n_objects posed objects -> ro_out, rd_out
+ * (n_objects, n_rays, 3), one launch.  poses: HOST array of n_objects x 12 floats, the object-to-world
+ * rotation R row-major, then the translation t.  fp32, every operation rounded, no FMA:
+ *   d = ro - t;  ro_out[i] = (d_0 R_0i + d_1 R_1i) + d_2 R_2i;  rd_out[i] the same with rd for d.
+ * The identity pose returns the input's values (a -0.0 component may come back as +0.0).  The outputs
+ * must not overlap the inputs.
+ * CN_EINVAL: a pointer NULL; n_rays <= 0; n_objects outside 1..CN_MAX_SCENE_OBJECTS; a pose entry
+ * that is not finite. */
+int cn_object_rays(const float* ro, const float* rd, int64_t n_rays, const float* poses, int n_objects,
+                   float* ro_out, float* rd_out, cn_stream_t stream);
+
 /* --- Iso-surface extraction (inference) ---------------------------------
  * A node grid to a triangle mesh, on the device: marching tetrahedra on the Kuhn (Freudenthal) split
  * of each cell.  The split is the same in every cell, so neighbouring cells agree on every shared
