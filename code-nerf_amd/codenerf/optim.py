@@ -186,7 +186,15 @@ class AdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         """One AdamW update of every parameter that has a gradient: ONE cn_adamw_step launch.
-        Parameters without a gradient keep their values and state, as in torch."""
+        Parameters without a gradient keep their values and state, as in torch.
+
+        Not graph-capturable: the step counts live on the host and are folded into the launch's
+        arguments, so a replay would repeat this step's; under capture it raises (use graph_scalars()
+        + graph_step())."""
+        if self._flat["param"].is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("codenerf.optim.AdamW.step() under graph capture: its step counts are host values "
+                               "baked into the launch, so every replay would repeat this one step; capture "
+                               "graph_step() and call graph_scalars() before each replay instead")
         loss = None
         if closure is not None:
             with torch.enable_grad():
