@@ -120,6 +120,12 @@ SIGNATURES = {
     "cn_scatter_rgb": (_i, [_p, _p, _i64, _p, _i64, _p]),
     "cn_volume_render_compose": (_i, [ctypes.POINTER(_p), _i, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p]),
     "cn_object_rays": (_i, [_p, _p, _i64, _fp, _i, _p, _p, _p]),
+    "cn_volume_render_compose_backward": (_i, [ctypes.POINTER(_p), _i, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p,
+                                               ctypes.POINTER(_p), _p, _i, _p]),
+    "cn_object_rays_backward_workspace_floats": (_i64, [_i64, _i]),
+    "cn_object_rays_backward": (_i, [_p, _p, _p, _p, _i64, _fp, _i, _p, _p, _i, _p, _p, _p]),
+    "cn_occupancy_gather": (_i, [_p, _p, _i64, _i64, _p, _p]),
+    "cn_occupancy_cull_backward": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "cn_isosurface_workspace_bytes": (_i64, [_i64]),
     "cn_isosurface_count": (_i, [_p, _i64, _f, _p, _p, _p]),
     "cn_isosurface_emit": (_i, [_p, _p, _i64, _f, _p, _i64, _i64, _p, _p, _p]),

@@ -347,6 +347,134 @@ def _c(t):
     return None if t is None else t.contiguous()
 
 
+# ------------------------------------------------------------------ scene rendering
+
+
+class ObjectRays(torch.autograd.Function):
+    """ops.object_rays: world rays in every posed object's frame -> ro, rd (K, R, 3); gradients w.r.t. the world
+    rays and the poses (K, 12) (R row-major, then t).  cn_object_rays takes host poses: ``rows`` (K rows of 12
+    host floats) when the caller has them, else the pose tensor is read back -- ONE HOST SYNCHRONISATION per
+    render."""
+
+    @staticmethod
+    def forward(ctx, ro, rd, poses, rows):
+        ctx.set_materialize_grads(False)
+        if rows is None:
+            rows = poses.detach().cpu().tolist()        # host synchronisation (see the docstring)
+        ctx.rows = rows
+        ctx.save_for_backward(ro, rd)
+        return ops.object_rays(ro, rd, rows)
+
+    @staticmethod
+    def backward(ctx, g_ro, g_rd):
+        if g_ro is None and g_rd is None:
+            return None, None, None, None
+        ro, rd = ctx.saved_tensors
+        needs = ctx.needs_input_grad
+        d_ro, d_rd, d_poses = ops.object_rays_backward(_c(g_ro), _c(g_rd), ro, rd, ctx.rows, want_ro=needs[0],
+                                                       want_rd=needs[1], want_poses=needs[2])
+        return d_ro, d_rd, d_poses, None
+
+
+class CullRows(torch.autograd.Function):
+    """ops.occupancy_cull's compact rows -> pts (M', 3), vdir (M', 3); ``holder["state"]`` receives the cull's
+    state (for ExpandRows) and ``holder["count"]`` M'.  Gradients w.r.t. ro and rd (z is detached); the kept
+    set is a constant."""
+
+    @staticmethod
+    def forward(ctx, ro, rd, z, chunk_rows, occupancy, holder):
+        ctx.set_materialize_grads(False)
+        count, _, pts, vdir, _, state = ops.occupancy_cull(ro, rd, z, chunk_rows, occupancy.bits, occupancy.resolution,
+                                                          occupancy.bound, want_code=False)
+        holder["state"], holder["count"] = state, count
+        ctx.state, ctx.chunk_rows = state, chunk_rows
+        ctx.save_for_backward(z)
+        return pts, vdir
+
+    @staticmethod
+    def backward(ctx, g_pts, g_vdir):
+        needs = ctx.needs_input_grad
+        if (g_pts is None and g_vdir is None) or not (needs[0] or needs[1]):
+            return (None,) * 6
+        (z,) = ctx.saved_tensors
+        d_ro, d_rd = ops.occupancy_cull_backward(_c(g_pts), _c(g_vdir), z, ctx.chunk_rows, ctx.state, want_ro=needs[0],
+                                                 want_rd=needs[1])
+        return d_ro, d_rd, None, None, None, None
+
+
+class ExpandRows(torch.autograd.Function):
+    """ops.occupancy_expand: the compact field result (M', 4) back at its samples -> raw (R, S, 4); the backward
+    gathers the kept rows' gradients (ops.occupancy_gather)."""
+
+    @staticmethod
+    def forward(ctx, raw_compact, holder):
+        ctx.state = holder["state"]
+        return ops.occupancy_expand(raw_compact, ctx.state)
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        return ops.occupancy_gather(g_raw.contiguous(), ctx.state), None
+
+
+class VolumeRenderCompose(torch.autograd.Function):
+    """ops.volume_render_compose -> rgb, disp, acc, weights, depth, acc_objects; gradients w.r.t. every object's
+    raw rows and rd (ops.volume_render_compose_backward)."""
+
+    @staticmethod
+    def forward(ctx, z, rd, *raws):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(z, rd, *raws)
+        return ops.volume_render_compose(raws, z, rd)
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_disp, g_acc, g_w, g_depth, g_ao):
+        z, rd, *raws = ctx.saved_tensors
+        if all(g is None for g in (g_rgb, g_disp, g_acc, g_w, g_depth, g_ao)):
+            return (None,) * (2 + len(raws))
+        d_raws, d_rd = ops.volume_render_compose_backward(raws, z, rd, _c(g_rgb), _c(g_disp), _c(g_acc), _c(g_w),
+                                                          _c(g_depth), _c(g_ao), want_rd=ctx.needs_input_grad[1])
+        return (None, d_rd, *d_raws)
+
+
+def object_rays_autograd(ro, rd, poses=None, rows=None):
+    """World rays in K objects' frames -> ro, rd (K, R, 3).  ``poses``: a (K, 12) device tensor (read to the
+    host: a synchronisation), or None with ``rows``, K host rows of 12 floats."""
+    if not _needs_grad(ro, rd, poses):
+        if rows is None:
+            rows = poses.detach().cpu().tolist()
+        return ops.object_rays(ro.detach(), rd.detach(), rows)
+    return ObjectRays.apply(ro, rd, poses, rows)
+
+
+def culled_field_autograd(model, ro, rd, z, z_s, z_t, occupancy, fx, fd):
+    """One object's field under its occupancy grid, differentiable w.r.t. its rays and codes (frozen weights):
+    CullRows -> the fused field in points mode over the M' kept rows (radiance_field_autograd with n_samples = 1,
+    rd = the rows' view directions, chunk_rows = M': the deterministic fused fp32 backward) -> ExpandRows
+    -> raw (R, S, 4).  M' is read back once (ops.occupancy_cull)."""
+    from .models.model import _field_op
+    z = z.detach()
+    holder = {}
+    if _needs_grad(ro, rd):
+        pts, vdir = CullRows.apply(ro, rd, z, ro.shape[0], occupancy, holder)
+    else:
+        count, _, pts, vdir, _, state = ops.occupancy_cull(ro.detach(), rd.detach(), z, ro.shape[0], occupancy.bits,
+                                                          occupancy.resolution, occupancy.bound, want_code=False)
+        holder["state"], holder["count"] = state, count
+    count = holder["count"]
+    if not count:
+        return ops.occupancy_expand(None, holder["state"])
+    raw = _field_op(model, z_s, z_t, vdir, count, fx, fd, pts=pts.view(count, 1, 3)).view(count, 4)
+    if not _needs_grad(raw):
+        return ops.occupancy_expand(raw.detach(), holder["state"])
+    return ExpandRows.apply(raw, holder)
+
+
+def volume_render_compose_autograd(raws, z, rd):
+    if not _needs_grad(rd, *raws):
+        return ops.volume_render_compose([r.detach() for r in raws], z.detach(), rd.detach())
+    return VolumeRenderCompose.apply(z.detach(), rd, *raws)
+
+
 # ------------------------------------------------------------------ field
 
 

@@ -26,7 +26,7 @@ from .volumetric_render import volume_render
 __all__ = ["RaySampler", "PointSampler", "PositionalEmbedder", "volume_render", "prepare_samplers",
            "prepare_embedders", "predict_radiance_and_render", "forward_pass", "parallel_image_render",
            "render_rays", "gather_rows", "gather_views", "density", "density_grid", "OccupancyGrid", "Mesh", "extract_mesh",
-           "density_gradient", "normals", "SceneObject", "render_scene"]
+           "density_gradient", "normals", "SceneObject", "render_scene", "render_scene_autograd", "rigid_pose"]
 
 
 def prepare_samplers(cfg, height: int, width: int, intrinsics, datatype, device) -> Tuple[RaySampler, PointSampler]:
@@ -701,6 +701,92 @@ def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: Poi
         rgb_f, disp_f, acc_f, _, depth_f, obj_f = ops.volume_render_compose(fields(fine_models, z_f, False), z_f, rd)
         out.update({"rgb_fine": rgb_f, "disp_fine": disp_f, "acc_fine": acc_f, "depth_fine": depth_f, "z_fine": z_f,
                     "acc_objects_fine": obj_f})
+    return out
+
+
+def rigid_pose(omega: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """A rigid pose from 6 numbers: the rotation vector ``omega`` (3,) (axis times angle, Rodrigues' formula) and
+    the translation ``t`` (3,) -> (12,): the object-to-world rotation row-major, then t -- a row of
+    render_scene_autograd's ``poses``.  Plain torch ops, differentiable; at omega = 0 it is the identity with
+    finite gradients (below |omega|^2 = 1e-8 the two coefficients are their Taylor series)."""
+    if omega.shape != (3,) or t.shape != (3,):
+        raise ValueError("omega and t must be (3,)")
+    th2 = (omega * omega).sum()
+    small = th2 < 1e-8
+    safe = torch.where(small, torch.ones_like(th2), th2)
+    th = safe.sqrt()
+    half = 0.5 * th
+    a = torch.where(small, 1.0 - th2 / 6.0, torch.sin(th) / th)                          # sin(th) / th
+    b = torch.where(small, 0.5 - th2 / 24.0, 0.5 * (torch.sin(half) / half) ** 2)        # (1 - cos(th)) / th^2
+    zero = torch.zeros_like(th2)
+    k = torch.stack([torch.stack([zero, -omega[2], omega[1]]), torch.stack([omega[2], zero, -omega[0]]),
+                     torch.stack([-omega[1], omega[0], zero])])
+    rot = torch.eye(3, dtype=omega.dtype, device=omega.device) + a * k + b * (k @ k)
+    return torch.cat([rot.reshape(9), t])
+
+
+def render_scene_autograd(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: PointSampler, embedders,
+                          coarse_model, fine_model=None, *, poses: Optional[torch.Tensor] = None,
+                          coarse_only: bool = False, t_rand: Optional[torch.Tensor] = None,
+                          u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """render_scene, differentiable: the same render and result dict (``coarse_rgb`` is always on), with
+    gradients w.r.t. every object's ``z_s`` / ``z_t``, the world rays ``ro`` / ``rd`` and ``poses`` -- so a scene
+    can be fitted to an image or to per-instance masks ("acc_objects_*").  ``poses``: an optional (K, 12) float32
+    device tensor that overrides the objects' host poses, each row the object-to-world rotation row-major, then
+    the translation (``rigid_pose`` builds one from 6 numbers); it is read to the host once per render, one host
+    synchronisation more than render_scene's 2 K.
+    The path per object and pass: autograd.CullRows -> the fused fp32 field in points mode over the kept rows
+    (frozen weights: its deterministic fused backward) -> autograd.ExpandRows; then autograd.VolumeRenderCompose.
+    Every backward kernel reduces in a fixed order, so two runs give the same gradients.  The kept sets, the fine
+    depths and the coarse weights that feed sample_pdf are constants (detached, as in the reference).
+    ValueError: a model parameter requires grad (frozen weights only), a model's precision is not "f32", or the
+    scene does not hold 1..8 SceneObjects."""
+    from ..autograd import culled_field_autograd, object_rays_autograd, volume_render_compose_autograd
+    objects = list(objects)
+    if not 1 <= len(objects) <= 8 or not all(isinstance(o, SceneObject) for o in objects):
+        raise ValueError(f"a scene holds 1..8 SceneObjects, got {len(objects)} entries")
+    coarse_models = [o.coarse_model if o.coarse_model is not None else coarse_model for o in objects]
+    fine_models = [o.fine_model if o.fine_model is not None else fine_model for o in objects]
+    if not coarse_only and any(m is None for m in fine_models):
+        raise ValueError("every object needs a fine model (its own or the scene's) unless coarse_only=True")
+    for m in coarse_models + ([] if coarse_only else fine_models):
+        if any(p.requires_grad for p in _unwrap(m).param_list()):
+            raise ValueError("render_scene_autograd differentiates codes, rays and poses with frozen weights: a "
+                             "model parameter requires grad (call model.requires_grad_(False))")
+        if getattr(_unwrap(m), "precision", "f32") != "f32":
+            raise ValueError(f"render_scene_autograd runs the fp32 field (precision \"f32\"), got "
+                             f"{_unwrap(m).precision!r}")
+    rows = None
+    if poses is None:
+        rows = [[v for row in o.rotation for v in row] + list(o.translation) for o in objects]
+    elif not (isinstance(poses, torch.Tensor) and poses.shape == (len(objects), 12) and poses.dtype == torch.float32
+              and poses.device == ro.device):
+        raise ValueError(f"poses must be a ({len(objects)}, 12) float32 tensor on the rays' device")
+    fx, fd = _check_embedders(embedders)
+    n = ro.shape[0]
+    ps = point_sampler
+    if ps.perturb and t_rand is None:
+        t_rand = torch.rand(n, ps.num_samples_coarse, dtype=torch.float32, device=ro.device)
+    _, z_c = ops.sample_uniform(ro.detach(), rd.detach(), ps.z_vals, ps.lower, ps.upper,
+                                t_rand if ps.perturb else None, want_pts=False)
+    ro_k, rd_k = (t.unbind(0) for t in object_rays_autograd(ro, rd, poses, rows))
+
+    def fields(models, z):
+        return [culled_field_autograd(_unwrap(m), ro_k[k], rd_k[k], z, o.z_s, o.z_t, o.occupancy, fx, fd)
+                for k, (o, m) in enumerate(zip(objects, models))]
+
+    rgb_c, disp_c, acc_c, w_c, depth_c, obj_c = volume_render_compose_autograd(fields(coarse_models, z_c), z_c, rd)
+    out = {"rgb_coarse": rgb_c, "disp_coarse": disp_c, "acc_coarse": acc_c, "weights_coarse": w_c,
+           "depth_coarse": depth_c, "z_coarse": z_c, "acc_objects_coarse": obj_c}
+    if coarse_only:
+        return out
+    if ps.perturb and u is None:
+        u = torch.rand(n, ps.num_samples_fine, dtype=torch.float32, device=ro.device)
+    _, z_f = ops.sample_pdf(ro.detach(), rd.detach(), w_c.detach()[..., 1:-1], z_c, ps.num_samples_fine,
+                            u if ps.perturb else ps.u_lin, want_pts=False)
+    rgb_f, disp_f, acc_f, _, depth_f, obj_f = volume_render_compose_autograd(fields(fine_models, z_f), z_f, rd)
+    out.update({"rgb_fine": rgb_f, "disp_fine": disp_f, "acc_fine": acc_f, "depth_fine": depth_f, "z_fine": z_f,
+                "acc_objects_fine": obj_f})
     return out
 
 

@@ -374,26 +374,40 @@ def volume_render_compose(raws: Sequence[Tensor], z: Tensor, rd: Tensor, want_we
     return rgb, disp, acc, w, depth, acc_objects
 
 
-def object_rays(ro: Tensor, rd: Tensor, poses) -> Tuple[Tensor, Tensor]:
-    """World rays (R, 3) in the frames of K posed objects (cn_object_rays) -> ro (K, R, 3), rd (K, R, 3).
-    ``poses``: K host (rotation (3, 3) row-major object-to-world, translation (3,)) pairs of floats; the
-    ray parameter is unchanged, so ro[k] + z rd[k] is the world point ro + z rd in object k's frame."""
-    lib = _lib_ready()
-    ro, rd = _cuda(ro, "ro"), _cuda(rd, "rd")
-    n = ro.shape[0]
-    assert ro.shape == (n, 3) and rd.shape == (n, 3), "ro / rd must be (num_rays, 3)"
+def _pose_rows(poses) -> list:
+    """K poses as 12 K host floats: each a (rotation (3, 3), translation (3,)) pair or a row of 12 (R row-major,
+    then t)."""
     poses = list(poses)
     assert 1 <= len(poses) <= _lib.CN_MAX_SCENE_OBJECTS, \
         f"a scene holds 1..{_lib.CN_MAX_SCENE_OBJECTS} objects, got {len(poses)}"
     flat = []
-    for rot, t in poses:
-        rows = [float(v) for row in rot for v in row] + [float(v) for v in t]
+    for pose in poses:
+        pose = list(pose)
+        if len(pose) == 2:
+            rot, t = pose
+            rows = [float(v) for row in rot for v in row] + [float(v) for v in t]
+        else:
+            rows = [float(v) for v in pose]
         assert len(rows) == 12, "a pose is a (3, 3) rotation and a (3,) translation"
         flat += rows
-    ro_out = torch.empty(len(poses), n, 3, device=ro.device, dtype=torch.float32)
-    rd_out = torch.empty(len(poses), n, 3, device=ro.device, dtype=torch.float32)
+    return flat
+
+
+def object_rays(ro: Tensor, rd: Tensor, poses) -> Tuple[Tensor, Tensor]:
+    """World rays (R, 3) in the frames of K posed objects (cn_object_rays) -> ro (K, R, 3), rd (K, R, 3).
+    ``poses``: K host (rotation (3, 3) row-major object-to-world, translation (3,)) pairs of floats, or K rows of
+    12 (the rotation row-major, then the translation); the ray parameter is unchanged, so ro[k] + z rd[k] is the
+    world point ro + z rd in object k's frame."""
+    lib = _lib_ready()
+    ro, rd = _cuda(ro, "ro"), _cuda(rd, "rd")
+    n = ro.shape[0]
+    assert ro.shape == (n, 3) and rd.shape == (n, 3), "ro / rd must be (num_rays, 3)"
+    flat = _pose_rows(poses)
+    k = len(flat) // 12
+    ro_out = torch.empty(k, n, 3, device=ro.device, dtype=torch.float32)
+    rd_out = torch.empty(k, n, 3, device=ro.device, dtype=torch.float32)
     if n:
-        check(lib.cn_object_rays(ptr(ro), ptr(rd), n, _lib.host_floats(flat), len(poses), ptr(ro_out), ptr(rd_out),
+        check(lib.cn_object_rays(ptr(ro), ptr(rd), n, _lib.host_floats(flat), k, ptr(ro_out), ptr(rd_out),
                                  stream_of(ro)), "cn_object_rays")
     return ro_out, rd_out
 
@@ -924,6 +938,119 @@ def volume_render_backward(raw: Tensor, z: Tensor, rd: Tensor, g_rgb=None, g_dis
                                         ptr(g_weights), ptr(g_depth), ptr(d_raw), ptr(d_rd),
                                         int(d_rd_into is not None), stream_of(raw)), "cn_volume_render_backward")
     return d_raw, d_rd
+
+
+def volume_render_compose_backward(raws: Sequence[Tensor], z: Tensor, rd: Tensor, g_rgb=None, g_disp=None, g_acc=None,
+                                   g_weights=None, g_depth=None, g_acc_objects=None, want_rd: bool = True,
+                                   d_rd_into: Optional[Tensor] = None) -> Tuple[list, Optional[Tensor]]:
+    """Gradient of volume_render_compose (cn_volume_render_compose_backward; the rule is in include/codenerf.h)
+    -> (d_raws: one (R, S, 4) tensor per object, d_rd (R, 3) or None).  The upstream gradients as
+    volume_render_backward's, plus ``g_acc_objects`` (K, R); ``d_rd_into``: d rd ADDED into it and returned."""
+    lib = _lib_ready()
+    raws = list(raws)
+    assert 1 <= len(raws) <= _lib.CN_MAX_SCENE_OBJECTS, \
+        f"a scene holds 1..{_lib.CN_MAX_SCENE_OBJECTS} objects, got {len(raws)}"
+    z, rd = _aligned16(_cuda(z, "depth_values")), _cuda(rd, "ray_directions")
+    n, s = z.shape
+    raws = [_aligned16(_cuda(raw, f"raws[{k}]")) for k, raw in enumerate(raws)]
+    for raw in raws:
+        assert raw.shape == (n, s, 4), "every radiance field must be (num_rays, num_samples, 4)"
+    assert rd.shape == (n, 3), "ray_directions must be (num_rays, 3)"
+    g_rgb, g_disp, g_acc, g_depth = (_opt(g_rgb, "g_rgb"), _opt(g_disp, "g_disp"), _opt(g_acc, "g_acc"),
+                                     _opt(g_depth, "g_depth"))
+    if g_weights is not None and g_weights.shape[-1] != s:   # S == 1: the reference's weights are (R, 0)
+        g_weights = None
+    g_weights, g_acc_objects = _opt(g_weights, "g_weights"), _opt(g_acc_objects, "g_acc_objects")
+    assert g_rgb is None or g_rgb.shape == (n, 3), "g_rgb must be (num_rays, 3)"
+    assert all(g is None or g.shape == (n,) for g in (g_disp, g_acc, g_depth)), "g_disp / g_acc / g_depth must be (num_rays,)"
+    assert g_weights is None or g_weights.shape == (n, s), "g_weights must be (num_rays, num_samples)"
+    assert g_acc_objects is None or g_acc_objects.shape == (len(raws), n), "g_acc_objects must be (num_objects, num_rays)"
+    d_raws = [torch.empty_like(raw) for raw in raws]
+    if d_rd_into is not None:
+        assert d_rd_into.is_cuda and d_rd_into.is_contiguous() and d_rd_into.shape == (n, 3)
+        d_rd = d_rd_into
+    else:
+        d_rd = torch.empty_like(rd) if want_rd else None
+    if n == 0:      # no rays: empty gradients (the C ABI refuses n_rays == 0), as the forward
+        return d_raws, d_rd
+    pointers, keep = _lib.pointer_array(raws)
+    outs, keep_outs = _lib.pointer_array(d_raws)
+    check(lib.cn_volume_render_compose_backward(pointers, len(raws), ptr(z), ptr(rd), n, s, ptr(g_rgb), ptr(g_disp),
+                                                ptr(g_acc), ptr(g_weights), ptr(g_depth), ptr(g_acc_objects), outs,
+                                                ptr(d_rd), int(d_rd_into is not None), stream_of(z)),
+          "cn_volume_render_compose_backward")
+    del keep, keep_outs
+    return d_raws, d_rd
+
+
+def object_rays_backward(g_ro_obj: Optional[Tensor], g_rd_obj: Optional[Tensor], ro: Tensor, rd: Tensor, poses,
+                         want_ro: bool = True, want_rd: bool = True, want_poses: bool = True,
+                         ray_into: Optional[Tuple[Tensor, Tensor]] = None):
+    """Gradient of object_rays (cn_object_rays_backward) -> (d_ro (R, 3), d_rd (R, 3), d_poses (K, 12): dR
+    row-major, then dt), each None when not wanted.  ``g_ro_obj`` / ``g_rd_obj`` (K, R, 3), either may be None
+    (zero); ``poses`` as object_rays takes them (or rows of 12).  ``ray_into``: (d_ro, d_rd) contiguous (R, 3)
+    device tensors the rays' gradients are ADDED into, and returned.  Deterministic: a fixed reduction order."""
+    lib = _lib_ready()
+    ro, rd = _cuda(ro, "ro"), _cuda(rd, "rd")
+    n = ro.shape[0]
+    assert ro.shape == (n, 3) and rd.shape == (n, 3), "ro / rd must be (num_rays, 3)"
+    flat = _pose_rows(poses)
+    k = len(flat) // 12
+    g_ro_obj, g_rd_obj = _opt(g_ro_obj, "g_ro_obj"), _opt(g_rd_obj, "g_rd_obj")
+    assert all(g is None or g.shape == (k, n, 3) for g in (g_ro_obj, g_rd_obj)), \
+        "g_ro_obj / g_rd_obj must be (num_objects, num_rays, 3)"
+    dev = ro.device
+    if ray_into is not None:
+        d_ro, d_rd = ray_into
+        assert all(t.is_cuda and t.is_contiguous() and t.shape == (n, 3) and t.dtype == torch.float32 for t in ray_into)
+    else:
+        d_ro = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_ro else None
+        d_rd = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_rd else None
+    d_poses = torch.empty(k, 12, device=dev, dtype=torch.float32) if want_poses else None
+    assert d_ro is not None or d_rd is not None or d_poses is not None, "nothing wanted"
+    if n == 0:
+        return d_ro, d_rd, (None if d_poses is None else d_poses.zero_())
+    workspace = None
+    if want_poses:
+        workspace = torch.empty(lib.cn_object_rays_backward_workspace_floats(n, k), device=dev, dtype=torch.float32)
+    check(lib.cn_object_rays_backward(ptr(g_ro_obj), ptr(g_rd_obj), ptr(ro), ptr(rd), n, _lib.host_floats(flat), k,
+                                      ptr(d_ro), ptr(d_rd), int(ray_into is not None), ptr(d_poses), ptr(workspace),
+                                      stream_of(ro)), "cn_object_rays_backward")
+    return d_ro, d_rd, d_poses
+
+
+def occupancy_gather(g_raw: Tensor, state) -> Tensor:
+    """Gradient of occupancy_expand (cn_occupancy_gather): ``g_raw`` (R, S, 4) -> the kept rows' gradients
+    (M', 4) in compact order; the culled slots' are dropped.  ``state``: occupancy_cull's."""
+    lib = _lib_ready()
+    workspace, n, s, k = state
+    g_raw = _aligned16(_cuda(g_raw, "g_raw"))
+    assert g_raw.shape == (n, s, 4), "g_raw must be (num_rays, num_samples, 4)"
+    g_compact = torch.empty(k, 4, device=g_raw.device, dtype=torch.float32)
+    if k:
+        check(lib.cn_occupancy_gather(ptr(g_raw), ptr(workspace), n, s, ptr(g_compact), stream_of(g_raw)),
+              "cn_occupancy_gather")
+    return g_compact
+
+
+def occupancy_cull_backward(g_pts: Optional[Tensor], g_vdir: Optional[Tensor], z: Tensor, chunk_rows: int, state,
+                            want_ro: bool = True, want_rd: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """Gradient of the rows occupancy_cull forms (cn_occupancy_cull_backward): ``g_pts`` / ``g_vdir`` (M', 3),
+    either may be None (zero) -> d_ro, d_rd (R, 3), each None when not wanted.  ``z``, ``chunk_rows`` and
+    ``state`` as in (and from) that occupancy_cull call.  Sequential fp32 sums in a fixed order: deterministic."""
+    lib = _lib_ready()
+    workspace, n, s, k = state
+    z = _cuda(z, "z_vals")
+    assert z.shape == (n, s), "z must be (num_rays, num_samples)"
+    g_pts, g_vdir = _opt(g_pts, "g_pts"), _opt(g_vdir, "g_vdir")
+    assert all(g is None or g.shape == (k, 3) for g in (g_pts, g_vdir)), f"g_pts / g_vdir must hold the {k} kept rows"
+    assert want_ro or want_rd, "nothing wanted"
+    d_ro = torch.empty(n, 3, device=z.device, dtype=torch.float32) if want_ro else None
+    d_rd = torch.empty(n, 3, device=z.device, dtype=torch.float32) if want_rd else None
+    if n * s:
+        check(lib.cn_occupancy_cull_backward(ptr(g_pts), ptr(g_vdir), ptr(z), ptr(workspace), n, s, int(chunk_rows),
+                                             ptr(d_ro), ptr(d_rd), stream_of(z)), "cn_occupancy_cull_backward")
+    return d_ro, d_rd
 
 
 def ray_bundle_backward(dirs: Tensor, batch: int, g_ro: Optional[Tensor], g_rd: Optional[Tensor]) -> Tensor:

@@ -360,3 +360,104 @@ extern "C" int cn_occupancy_expand(const float* raw_compact, const void* workspa
                      static_cast<int>(n_samples), reinterpret_cast<float4*>(raw));
   return cn::launch_status();
 }
+
+// ---------------------------------------------------------------- backward of the compact rows
+namespace {
+
+// cn_occupancy_expand's backward, one wave per ray as the expand: a kept sample's gradient row to its compact
+// row; a culled slot's is dropped (the empty row is a constant).
+__global__ __launch_bounds__(64 * kRayWaves) void occupancy_gather_kernel(
+    const float4* __restrict__ g_raw, const int* __restrict__ offsets, const unsigned long long* __restrict__ masks,
+    int64_t n_rays, int n_samples, float4* __restrict__ g_compact) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = blockIdx.x * static_cast<int64_t>(kRayWaves) + (threadIdx.x >> 6);
+  if (r >= n_rays) return;                 // wave-uniform
+  const int nw = static_cast<int>(mask_words(n_samples));
+  int64_t j0 = offsets[r];
+  for (int w = 0; w < nw; ++w) {
+    const unsigned long long m = masks[r * nw + w];
+    const int s = 64 * w + lane;
+    if (s < n_samples && ((m >> lane) & 1ull)) g_compact[j0 + rank_below(m)] = g_raw[r * n_samples + s];
+    j0 += __popcll(m);
+  }
+}
+
+// The compact row of kept sample s of a ray whose first row is j0: the kept samples before it.
+__device__ __forceinline__ int64_t row_of(const unsigned long long* __restrict__ m, int64_t j0, int s) {
+  for (int w = 0; w < (s >> 6); ++w) j0 += __popcll(m[w]);
+  return j0 + __popcll(m[s >> 6] & ((1ull << (s & 63)) - 1ull));
+}
+
+// cn_occupancy_cull's backward: one lane per (ray, component), every sum sequential in the header's order.
+__global__ __launch_bounds__(256) void occupancy_cull_backward_kernel(
+    const float* __restrict__ g_pts, const float* __restrict__ g_vdir, const float* __restrict__ z, int64_t n_rays,
+    int n_samples, int64_t chunk_rows, const int* __restrict__ offsets, const unsigned long long* __restrict__ masks,
+    float* __restrict__ d_ro, float* __restrict__ d_rd) {
+  const int64_t t = blockIdx.x * static_cast<int64_t>(256) + threadIdx.x;
+  if (t >= 3 * n_rays) return;
+  const int64_t r = t / 3;
+  const int c = static_cast<int>(t - 3 * r);
+  const int nw = static_cast<int>(mask_words(n_samples));
+  float so = 0.0f, sp = 0.0f, sv = 0.0f;
+  if (g_pts) {
+    int64_t j = offsets[r];
+    for (int w = 0; w < nw; ++w) {
+      unsigned long long m = masks[r * nw + w];
+      while (m) {                          // ascending samples: ascending rows
+        const int s = 64 * w + __builtin_ctzll(m);
+        m &= m - 1;
+        const float g = g_pts[3 * j + c];
+        so = __fadd_rn(so, g);
+        sp = __fadd_rn(sp, __fmul_rn(z[r * n_samples + s], g));
+        ++j;
+      }
+    }
+  }
+  if (g_vdir) {
+    // the samples whose Q1 view-direction ray is r: k' = (r - base) + i rcnt of the chunk, ascending
+    const int64_t base = (r / chunk_rows) * chunk_rows;
+    const int64_t rcnt = min(chunk_rows, n_rays - base);
+    for (int i = 0; i < n_samples; ++i) {
+      const int64_t kk = (r - base) + i * rcnt;          // < rcnt S
+      const int64_t rr = base + kk / n_samples;
+      const int s = static_cast<int>(kk % n_samples);
+      const unsigned long long* m = masks + rr * nw;
+      if ((m[s >> 6] >> (s & 63)) & 1ull) sv = __fadd_rn(sv, g_vdir[3 * row_of(m, offsets[rr], s) + c]);
+    }
+  }
+  if (d_ro) d_ro[t] = so;
+  if (d_rd) d_rd[t] = __fadd_rn(sp, sv);
+}
+
+}  // namespace
+
+extern "C" int cn_occupancy_gather(const float* g_raw, const void* workspace, int64_t n_rays, int64_t n_samples,
+                                   float* g_compact, cn_stream_t stream) {
+  CN_CHECK_ARG(g_raw && workspace && g_compact && sizes_ok(n_rays, n_samples));
+  CN_CHECK_ARG(aligned8(workspace) && cn::aligned16(g_raw) && cn::aligned16(g_compact));
+  const int64_t ray_blocks = cn::ceil_div(n_rays, kRayWaves);
+  CN_CHECK_ARG(ray_blocks <= INT_MAX);
+  const int* offsets = static_cast<const int*>(workspace);
+  const unsigned long long* masks =
+      reinterpret_cast<const unsigned long long*>(static_cast<const char*>(workspace) + offsets_bytes(n_rays));
+  hipLaunchKernelGGL(occupancy_gather_kernel, dim3(static_cast<unsigned>(ray_blocks)), dim3(64 * kRayWaves), 0,
+                     cn::as_stream(stream), reinterpret_cast<const float4*>(g_raw), offsets, masks, n_rays,
+                     static_cast<int>(n_samples), reinterpret_cast<float4*>(g_compact));
+  return cn::launch_status();
+}
+
+extern "C" int cn_occupancy_cull_backward(const float* g_pts, const float* g_vdir, const float* z, const void* workspace,
+                                          int64_t n_rays, int64_t n_samples, int64_t chunk_rows, float* d_ro,
+                                          float* d_rd, cn_stream_t stream) {
+  CN_CHECK_ARG(z && workspace && (d_ro || d_rd) && sizes_ok(n_rays, n_samples) && chunk_rows > 0);
+  CN_CHECK_ARG(aligned8(workspace));
+  const int64_t blocks = cn::ceil_div(3 * n_rays, 256);
+  CN_CHECK_ARG(blocks <= INT_MAX);
+  const int* offsets = static_cast<const int*>(workspace);
+  const unsigned long long* masks =
+      reinterpret_cast<const unsigned long long*>(static_cast<const char*>(workspace) + offsets_bytes(n_rays));
+  hipLaunchKernelGGL(occupancy_cull_backward_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+                     cn::as_stream(stream), g_pts, g_vdir, z, n_rays, static_cast<int>(n_samples), chunk_rows, offsets,
+                     masks, d_ro, d_rd);
+  return cn::launch_status();
+}

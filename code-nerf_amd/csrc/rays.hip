@@ -222,3 +222,136 @@ extern "C" int cn_gather_rays_backward(const float* g_ro, const float* g_rd, int
                      cn::as_stream(stream), g_ro, g_rd, batch, hw, select_inds, sample_size, d_ro, d_rd);
   return cn::launch_status();
 }
+
+// ---------------------------------------------------------------- scene objects, backward
+// Gradient of cn_object_rays (the rule is in include/codenerf.h).  One lane per ray sums the objects'
+// gradients into the ray's d ro / d rd (one writer per element) and forms the ray's 12 pose terms per object;
+// a block's lanes walk the rays in a fixed stride, its 12 sums per object are reduced by the fixed LDS tree of
+// ray_bundle_backward_kernel into the workspace's block partials, and a second launch reduces the partials, one
+// block per object, in the same fixed order: no atomics, two runs give the same bits.
+namespace {
+
+constexpr int kPoseBlocks = 256;  // at most: block partials per object
+
+inline int pose_blocks(int64_t n_rays) {
+  return static_cast<int>(cn::ceil_div(n_rays, 256) < kPoseBlocks ? cn::ceil_div(n_rays, 256) : kPoseBlocks);
+}
+
+// The tree over the block's 256 lanes of 12 sums each -> out[0..12) (from lanes 0..11).
+__device__ __forceinline__ void reduce12(float (&red)[12][256], const float (&acc)[12], float* __restrict__ out) {
+#pragma unroll
+  for (int e = 0; e < 12; ++e) red[e][threadIdx.x] = acc[e];
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s)
+#pragma unroll
+      for (int e = 0; e < 12; ++e) red[e][threadIdx.x] += red[e][threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x < 12) out[threadIdx.x] = red[threadIdx.x][0];
+  __syncthreads();  // red is rewritten by the next object
+}
+
+__global__ __launch_bounds__(256) void object_rays_backward_kernel(
+    const float* __restrict__ g_ro, const float* __restrict__ g_rd, const float* __restrict__ ro,
+    const float* __restrict__ rd, int64_t n_rays, ObjectPoses poses, int n_objects, float* __restrict__ d_ro,
+    float* __restrict__ d_rd, int accumulate, float* __restrict__ partials) {
+  __shared__ float red[12][256];
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const int64_t first = blockIdx.x * (int64_t)256 + threadIdx.x;
+  // the rays' own gradients: sum_k R_k g_k, ascending k
+  if (d_ro || d_rd) {
+    for (int64_t r = first; r < n_rays; r += stride) {
+      float so[3] = {0.f, 0.f, 0.f}, sv[3] = {0.f, 0.f, 0.f};
+      for (int k = 0; k < n_objects; ++k) {
+        const float* m = poses.p[k];
+        const int64_t q = 3 * (k * n_rays + r);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const float go = g_ro ? g_ro[q + i] : 0.0f, gv = g_rd ? g_rd[q + i] : 0.0f;
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            so[j] += m[3 * j + i] * go;
+            sv[j] += m[3 * j + i] * gv;
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        if (d_ro) d_ro[3 * r + j] = accumulate ? d_ro[3 * r + j] + so[j] : so[j];
+        if (d_rd) d_rd[3 * r + j] = accumulate ? d_rd[3 * r + j] + sv[j] : sv[j];
+      }
+    }
+  }
+  if (!partials) return;  // uniform: no pose gradient wanted
+  for (int k = 0; k < n_objects; ++k) {
+    const float* m = poses.p[k];
+    float acc[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) acc[e] = 0.0f;
+    for (int64_t r = first; r < n_rays; r += stride) {
+      const int64_t q = 3 * (k * n_rays + r);
+      float go[3], gv[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        go[i] = g_ro ? g_ro[q + i] : 0.0f;
+        gv[i] = g_rd ? g_rd[q + i] : 0.0f;
+      }
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const float dj = ro[3 * r + j] - m[9 + j], vj = rd[3 * r + j];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          acc[3 * j + i] += dj * go[i] + vj * gv[i];
+          acc[9 + j] -= m[3 * j + i] * go[i];
+        }
+      }
+    }
+    reduce12(red, acc, partials + ((int64_t)k * gridDim.x + blockIdx.x) * 12);
+  }
+}
+
+// Stage 2, one block per object: lane t sums the block partials t, t + 256, ... (at most one with
+// kPoseBlocks = 256), then the tree.
+__global__ __launch_bounds__(256) void object_poses_reduce_kernel(const float* __restrict__ partials, int n_blocks,
+                                                                  float* __restrict__ d_poses) {
+  __shared__ float red[12][256];
+  const int k = blockIdx.x;
+  float acc[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) acc[e] = 0.0f;
+  for (int b = threadIdx.x; b < n_blocks; b += 256)
+#pragma unroll
+    for (int e = 0; e < 12; ++e) acc[e] += partials[((int64_t)k * n_blocks + b) * 12 + e];
+  reduce12(red, acc, d_poses + 12 * k);
+}
+
+}  // namespace
+
+extern "C" int64_t cn_object_rays_backward_workspace_floats(int64_t n_rays, int n_objects) {
+  if (n_rays <= 0 || n_objects < 1 || n_objects > CN_MAX_SCENE_OBJECTS) return -1;
+  return (int64_t)pose_blocks(n_rays) * n_objects * 12;
+}
+
+extern "C" int cn_object_rays_backward(const float* g_ro_obj, const float* g_rd_obj, const float* ro, const float* rd,
+                                       int64_t n_rays, const float* poses, int n_objects, float* d_ro, float* d_rd,
+                                       int accumulate, float* d_poses, float* workspace, cn_stream_t stream) {
+  CN_CHECK_ARG(ro && rd && poses && n_rays > 0 && (accumulate == 0 || accumulate == 1));
+  CN_CHECK_ARG(n_objects >= 1 && n_objects <= CN_MAX_SCENE_OBJECTS);
+  CN_CHECK_ARG(d_ro || d_rd || d_poses);
+  CN_CHECK_ARG(!d_poses || workspace);
+  ObjectPoses p = {};
+  for (int k = 0; k < n_objects; ++k)
+    for (int e = 0; e < 12; ++e) {
+      const float v = poses[12 * k + e];
+      CN_CHECK_ARG(v - v == 0.0f);  // finite
+      p.p[k][e] = v;
+    }
+  const int blocks = pose_blocks(n_rays);
+  hipStream_t st = cn::as_stream(stream);
+  hipLaunchKernelGGL(object_rays_backward_kernel, dim3(blocks), dim3(256), 0, st, g_ro_obj, g_rd_obj, ro, rd, n_rays, p,
+                     n_objects, d_ro, d_rd, accumulate, d_poses ? workspace : nullptr);
+  if (d_poses)
+    hipLaunchKernelGGL(object_poses_reduce_kernel, dim3(n_objects), dim3(256), 0, st, workspace, blocks, d_poses);
+  return cn::launch_status();
+}

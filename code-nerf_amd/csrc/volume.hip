@@ -613,6 +613,124 @@ extern "C" int cn_volume_render_compose(const float* const* raws, int n_objects,
 // z is never differentiated (the reference detaches its samples).  Same layout as the forward.
 namespace {
 
+// The device arithmetic volume_render_backward_kernel and volume_render_compose_backward_kernel share: every
+// function is the plain kernel's own expressions (the build does not contract, so the bits are its bits).
+
+// The forward's weights again, from this lane's run of densities sig (0 outside the run): dist, sd, the
+// transmittances tr, the weights w, and the ray's depth / acc in every lane of the ray.
+template <int K, int L>
+__device__ __forceinline__ void backward_weights(const float (&zz)[K], const float (&sig)[K], int S, int run, int j0,
+                                                 float nrm, float (&dist)[K], float (&sd)[K], float (&w)[K],
+                                                 float (&tr)[K], float& dep_out, float& ac_out) {
+  const float znext = next_lane<L>(zz[0]);
+  double run_sum = 0.0;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const int j = j0 + i;
+    sd[i] = 0.0f;
+    dist[i] = 0.0f;
+    if (i < run && j < S) {
+      const float zn = (i + 1 < run) ? zz[(i + 1) % K] : znext;
+      dist[i] = (j + 1 < S) ? __fsub_rn(zn, zz[i]) : 1e10f;
+      sd[i] = __fmul_rn(sig[i], __fmul_rn(dist[i], nrm));
+      if (j + 1 < S) run_sum += static_cast<double>(sd[i]);
+    }
+  }
+  double prefix = ray_exclusive_scan<L>(run_sum);
+  float dep = 0.f, ac = 0.f;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const int j = j0 + i;
+    w[i] = 0.0f;
+    tr[i] = 0.0f;
+    if (i < run && j < S) {
+      tr[i] = expf(-static_cast<float>(prefix));
+      w[i] = __fmul_rn(__fsub_rn(1.0f, expf(-sd[i])), tr[i]);
+      dep += w[i] * zz[i];
+      ac += w[i];
+      if (j + 1 < S) prefix += static_cast<double>(sd[i]);
+    }
+  }
+  dep_out = ray_sum_all<L>(dep);
+  ac_out = ray_sum_all<L>(ac);
+}
+
+// The ray's upstream gradients (a NULL one is zero), g_disp folded into g_depth / g_acc.
+struct RayGrads {
+  float r0, r1, r2, dep, acc;
+};
+__device__ __forceinline__ RayGrads ray_grads(int64_t r, float dep, float ac, const float* __restrict__ g_rgb,
+                                              const float* __restrict__ g_disp, const float* __restrict__ g_acc,
+                                              const float* __restrict__ g_depth) {
+  RayGrads g;
+  g.r0 = g_rgb ? g_rgb[3 * r] : 0.f;
+  g.r1 = g_rgb ? g_rgb[3 * r + 1] : 0.f;
+  g.r2 = g_rgb ? g_rgb[3 * r + 2] : 0.f;
+  g.dep = g_depth ? g_depth[r] : 0.f;
+  g.acc = g_acc ? g_acc[r] : 0.f;
+  if (g_disp) {
+    const float q = dep / ac;
+    if (q > 1e-10f) {  // d(1/q)/dq = -1/q^2; below the clamp torch routes the gradient to the constant
+      const float gq = -g_disp[r] / (q * q);
+      g.dep += gq / ac;
+      g.acc += gq * (-dep / (ac * ac));
+    }
+  }
+  return g;
+}
+
+// G = dL/dw of a sample of colour (c0, c1, c2) at depth zv with weight gradient gw.
+__device__ __forceinline__ float weight_grad(const RayGrads& g, float c0, float c1, float c2, float zv, float gw) {
+  return g.r0 * c0 + g.r1 * c1 + g.r2 * c2 + g.dep * zv + g.acc + gw;
+}
+
+// d raw colour channel from the channel's sigmoid s: w g 1.002 s (1 - s).
+__device__ __forceinline__ float colour_grad(float w, float g, float s) { return w * g * 1.002f * s * (1.0f - s); }
+
+// softplus20'(x - 1) of a raw density x.
+__device__ __forceinline__ float sigma_slope(float xs) {
+  const float x = xs - 1.0f;
+  return x > 20.0f ? 1.0f : cn::sigmoid_hw(x);
+}
+
+// dL/dsd per sample from G (the reverse ray scan), and this lane's part of sum dL/dsd sigma dist.
+template <int K, int L>
+__device__ __forceinline__ void backward_dsd(const float (&G)[K], const float (&w)[K], const float (&tr)[K],
+                                             const float (&sd)[K], const float (&sig)[K], const float (&dist)[K], int S,
+                                             int run, int j0, float (&dsd)[K], float& gnorm_out) {
+  float gw_run = 0.f;
+#pragma unroll
+  for (int i = 0; i < K; ++i)
+    if (i < run && j0 + i < S) gw_run += G[i] * w[i];
+  float suffix = ray_exclusive_suffix<L>(gw_run);  // sum of G_j w_j over later lanes' runs
+  float gnorm = 0.f;
+#pragma unroll
+  for (int i = K - 1; i >= 0; --i) {
+    dsd[i] = 0.0f;
+    if (i < run && j0 + i < S) {
+      dsd[i] = G[i] * tr[i] * expf(-sd[i]) - suffix;
+      suffix += G[i] * w[i];
+      gnorm += dsd[i] * sig[i] * dist[i];
+    }
+  }
+  gnorm_out = gnorm;
+}
+
+// d rd = (sum dL/dsd sigma dist) rd / |rd| from the lane that holds the ray's sum: one writer per ray.
+__device__ __forceinline__ void store_d_rd(float* __restrict__ d_rd, int64_t r, float gnorm, float nrm, float d0,
+                                           float d1, float d2, int accumulate_rd) {
+  const float inv = nrm > 0.f ? gnorm / nrm : 0.f;
+  if (accumulate_rd) {      // the caller's running sum of the ray's gradients
+    d_rd[3 * r] += inv * d0;
+    d_rd[3 * r + 1] += inv * d1;
+    d_rd[3 * r + 2] += inv * d2;
+  } else {
+    d_rd[3 * r] = inv * d0;
+    d_rd[3 * r + 1] = inv * d1;
+    d_rd[3 * r + 2] = inv * d2;
+  }
+}
+
 template <int K, bool FULL, int L>
 __global__ __launch_bounds__(256) void volume_render_backward_kernel(
     const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ rd,
@@ -648,53 +766,13 @@ __global__ __launch_bounds__(256) void volume_render_backward_kernel(
   load_depths<K>(zr, j0, run, S_in, zz);
   if (live) load_raw_lds<K>(sl, q0, j0, run, S_in, rv);
   else load_run<K>(zr, rr, j0, run, S_in, zz, rv);  // the last ray again (not in this wave's block)
-  const float znext = next_lane<L>(zz[0]);
-  double run_sum = 0.0;
 #pragma unroll
-  for (int i = 0; i < K; ++i) {
-    const int j = j0 + i;
-    sd[i] = 0.0f;
-    dist[i] = 0.0f;
-    sig[i] = 0.0f;
-    if (i < run && j < S) {
-      const float zn = (i + 1 < run) ? zz[(i + 1) % K] : znext;
-      dist[i] = (j + 1 < S) ? __fsub_rn(zn, zz[i]) : 1e10f;
-      sig[i] = cn::softplus20(__fsub_rn(rv[i].w, 1.0f));
-      sd[i] = __fmul_rn(sig[i], __fmul_rn(dist[i], nrm));
-      if (j + 1 < S) run_sum += static_cast<double>(sd[i]);
-    }
-  }
-  double prefix = ray_exclusive_scan<L>(run_sum);
-  float dep = 0.f, ac = 0.f;
-#pragma unroll
-  for (int i = 0; i < K; ++i) {
-    const int j = j0 + i;
-    w[i] = 0.0f;
-    tr[i] = 0.0f;
-    if (i < run && j < S) {
-      tr[i] = expf(-static_cast<float>(prefix));
-      w[i] = __fmul_rn(__fsub_rn(1.0f, expf(-sd[i])), tr[i]);
-      dep += w[i] * zz[i];
-      ac += w[i];
-      if (j + 1 < S) prefix += static_cast<double>(sd[i]);
-    }
-  }
-  // the ray's depth / acc in every lane of the ray
-  dep = ray_sum_all<L>(dep);
-  ac = ray_sum_all<L>(ac);
-  const float gr0 = g_rgb ? g_rgb[3 * r] : 0.f, gr1 = g_rgb ? g_rgb[3 * r + 1] : 0.f;
-  const float gr2 = g_rgb ? g_rgb[3 * r + 2] : 0.f;
-  float gdep = g_depth ? g_depth[r] : 0.f, gacc = g_acc ? g_acc[r] : 0.f;
-  if (g_disp) {
-    const float q = dep / ac;
-    if (q > 1e-10f) {  // d(1/q)/dq = -1/q^2; below the clamp torch routes the gradient to the constant
-      const float gq = -g_disp[r] / (q * q);
-      gdep += gq / ac;
-      gacc += gq * (-dep / (ac * ac));
-    }
-  }
+  for (int i = 0; i < K; ++i) sig[i] = (i < run && j0 + i < S) ? raw_sigma(rv[i].w) : 0.0f;
+  float dep, ac;
+  backward_weights<K, L>(zz, sig, S, run, j0, nrm, dist, sd, w, tr, dep, ac);
+  const RayGrads g = ray_grads(r, dep, ac, g_rgb, g_disp, g_acc, g_depth);
   // G_i and the per-sample colour gradients
-  float G[K], gw_run = 0.f;
+  float G[K], dsd[K];
 #pragma unroll
   for (int i = 0; i < K; ++i) {
     const int j = j0 + i;
@@ -702,27 +780,21 @@ __global__ __launch_bounds__(256) void volume_render_backward_kernel(
     if (i < run && j < S) {
       const float s0 = cn::sigmoid_hw(rv[i].x), s1 = cn::sigmoid_hw(rv[i].y), s2 = cn::sigmoid_hw(rv[i].z);
       const float c0 = s0 * 1.002f - 0.001f, c1 = s1 * 1.002f - 0.001f, c2 = s2 * 1.002f - 0.001f;
-      G[i] = gr0 * c0 + gr1 * c1 + gr2 * c2 + gdep * zz[i] + gacc + (g_w ? g_w[r * S_in + j] : 0.f);
-      rv[i].x = w[i] * gr0 * 1.002f * s0 * (1.0f - s0);  // reuse rv for d_raw[0:3]
-      rv[i].y = w[i] * gr1 * 1.002f * s1 * (1.0f - s1);
-      rv[i].z = w[i] * gr2 * 1.002f * s2 * (1.0f - s2);
-      gw_run += G[i] * w[i];
+      G[i] = weight_grad(g, c0, c1, c2, zz[i], g_w ? g_w[r * S_in + j] : 0.f);
+      rv[i].x = colour_grad(w[i], g.r0, s0);  // reuse rv for d_raw[0:3]
+      rv[i].y = colour_grad(w[i], g.r1, s1);
+      rv[i].z = colour_grad(w[i], g.r2, s2);
     }
   }
-  float suffix = ray_exclusive_suffix<L>(gw_run);  // sum of G_j w_j over later lanes' runs
-  float gnorm = 0.f;
+  float gnorm;
+  backward_dsd<K, L>(G, w, tr, sd, sig, dist, S, run, j0, dsd, gnorm);
 #pragma unroll
   for (int i = K - 1; i >= 0; --i) {
     const int j = j0 + i;
     if (i < run && j < S) {
-      const float dsd = G[i] * tr[i] * expf(-sd[i]) - suffix;
-      suffix += G[i] * w[i];
-      const float x = rv[i].w - 1.0f;
-      const float dsp = x > 20.0f ? 1.0f : cn::sigmoid_hw(x);
       float4 o = rv[i];
-      o.w = dsd * (dist[i] * nrm) * dsp;
+      o.w = dsd[i] * (dist[i] * nrm) * sigma_slope(rv[i].w);
       if (live) sl[pad4(q0 + i)] = o;
-      gnorm += dsd * sig[i] * dist[i];
     } else if (i < run && j < S_in) {
       if (live) sl[pad4(q0 + i)] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -730,18 +802,7 @@ __global__ __launch_bounds__(256) void volume_render_backward_kernel(
   __builtin_amdgcn_wave_barrier();  // the copy-out reads quads other lanes wrote
   stage_rows_out<K>(reinterpret_cast<float4*>(d_raw) + rw0 * S_in, nq, sl, lane);
   gnorm = ray_sum<L>(gnorm);
-  if (live && sub == (L == 16 ? 15 : 63) && d_rd) {
-    const float inv = nrm > 0.f ? gnorm / nrm : 0.f;
-    if (accumulate_rd) {      // one writer per ray: the caller's running sum of the ray's gradients
-      d_rd[3 * r] += inv * d0;
-      d_rd[3 * r + 1] += inv * d1;
-      d_rd[3 * r + 2] += inv * d2;
-    } else {
-      d_rd[3 * r] = inv * d0;
-      d_rd[3 * r + 1] = inv * d1;
-      d_rd[3 * r + 2] = inv * d2;
-    }
-  }
+  if (live && sub == (L == 16 ? 15 : 63) && d_rd) store_d_rd(d_rd, r, gnorm, nrm, d0, d1, d2, accumulate_rd);
 }
 
 }  // namespace
@@ -757,5 +818,219 @@ extern "C" int cn_volume_render_backward(const float* raw, const float* z, const
   CN_VOLUME_DISPATCH(volume_render_backward_kernel, n_samples, n_rays, cn::as_stream(stream), raw, z, rd, n_rays,
                      static_cast<int>(n_samples), g_rgb, g_disp, g_acc, g_weights, g_depth, d_raw, d_rd,
                      accumulate_rd);
+  return cn::launch_status();
+}
+
+// ---------------------------------------------------------------- scene composition, backward
+// Gradient of cn_volume_render_compose w.r.t. every object's raw rows and rd (the rule is in
+// include/codenerf.h): the composition read as real functions, every sample's active set held fixed.  The
+// forward's geometry.  Pass 1 stages each object's rows in turn and keeps, per sample, the summed density, the
+// colour numerator, the count of active objects, the last active colour and (with g_acc_objects) the
+// density-weighted sum of the objects' mask gradients; then the plain backward's arithmetic on the summed
+// density and the mixed colour gives dL/dsd; pass 2 stages each object's rows again, recomputes its density
+// and colours (nothing per object stays in registers between the passes) and sends its d raw rows out through
+// the same LDS block.  With one active object at a sample its row gets volume_render_backward_kernel's bits.
+// Algorithmic bytes per ray: 12 (rd) + (32 n_objects + 4) S in, 16 n_objects S + 12 out, plus the upstream rows.
+namespace {
+
+struct ComposeGrads {
+  float* p[CN_MAX_SCENE_OBJECTS];
+};
+
+template <int K, int L, int NOBJ>
+__global__ __launch_bounds__(256) void volume_render_compose_backward_kernel(
+    ComposeRaws raws, int n_objects, const float* __restrict__ z, const float* __restrict__ rd, int64_t n_rays,
+    int S_in, const float* __restrict__ g_rgb, const float* __restrict__ g_disp, const float* __restrict__ g_acc,
+    const float* __restrict__ g_w, const float* __restrict__ g_depth, const float* __restrict__ g_ao,
+    ComposeGrads d_raws, float* __restrict__ d_rd, int accumulate_rd) {
+  static_assert(K <= kMaxRun && (L == 16 || L == 64) && NOBJ >= 1 && NOBJ <= CN_MAX_SCENE_OBJECTS, "instance");
+  __shared__ float4 slds[4 * 80 * K];  // per wave: one object's rows in, then its d raw rows out
+  const int sub = threadIdx.x & (L - 1), lane = threadIdx.x & 63;
+  const int64_t r = ((int64_t)blockIdx.x * 256 + threadIdx.x) / L;
+  const int64_t rw0 = r - lane / L;  // the wave's first ray
+  if (rw0 >= n_rays) return;         // the whole wave
+  const int nq = static_cast<int>(min<int64_t>(64 / L, n_rays - rw0)) * S_in;  // the wave's valid quads
+  float4* sl = slds + (threadIdx.x >> 6) * 80 * K;
+  // a ray past n_rays (L = 16 only) takes part in the wave's copies alone: whole rows of 16 lanes skip the
+  // arithmetic together, so no cross-lane step reads one
+  const bool live = r < n_rays;
+  const int S = S_in == 1 ? 0 : S_in;  // see render_run: S == 1 has no contributing sample
+  const int run = (S_in + L - 1) / L;
+  const int j0 = sub * run;
+  const int q0 = (lane / L) * S_in + j0;  // this run's first quad in the wave block
+  float zz[K];
+  float nrm = 0.0f, d0 = 0.0f, d1 = 0.0f, d2 = 0.0f;
+#pragma unroll
+  for (int i = 0; i < K; ++i) zz[i] = 0.0f;
+  if (live) {
+    load_depths<K>(z + r * S_in, j0, run, S_in, zz);
+    d0 = rd[3 * r], d1 = rd[3 * r + 1], d2 = rd[3 * r + 2];
+    nrm = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+  }
+  float gao[NOBJ];  // the ray's mask gradients
+#pragma unroll
+  for (int k = 0; k < NOBJ; ++k) gao[k] = (g_ao && live && k < n_objects) ? g_ao[k * n_rays + r] : 0.0f;
+
+  // pass 1: the forward's mix
+  float sig[K], num[K][3], lone[K][3], aon[K], alone[K];
+  int cnt[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    sig[i] = aon[i] = alone[i] = 0.0f;
+    cnt[i] = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) num[i][c] = lone[i][c] = 0.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < NOBJ; ++k) {
+    if (k >= n_objects) continue;  // uniform
+    __builtin_amdgcn_wave_barrier();  // (see the forward)
+    stage_rows_in<K>(reinterpret_cast<const float4*>(raws.p[k]) + rw0 * S_in, nq, sl, lane);
+    __builtin_amdgcn_wave_barrier();
+    if (!live) continue;
+    float4 rv[K];
+    load_raw_lds<K>(sl, q0, j0, run, S_in, rv);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      if (i < run && j0 + i < S) {
+        const float s = raw_sigma(rv[i].w);
+        sig[i] = __fadd_rn(sig[i], s);
+        if (s != 0.0f) {  // active (a NaN density is)
+          const float c0 = raw_colour(rv[i].x), c1 = raw_colour(rv[i].y), c2 = raw_colour(rv[i].z);
+          cnt[i] += 1;
+          lone[i][0] = c0;
+          lone[i][1] = c1;
+          lone[i][2] = c2;
+          num[i][0] = __fadd_rn(num[i][0], __fmul_rn(s, c0));
+          num[i][1] = __fadd_rn(num[i][1], __fmul_rn(s, c1));
+          num[i][2] = __fadd_rn(num[i][2], __fmul_rn(s, c2));
+          alone[i] = gao[k];
+          aon[i] += gao[k] * s;
+        }
+      }
+    }
+  }
+
+  // dL/dsd from the summed density and the mixed colour: the plain backward's arithmetic
+  float dist[K], w[K], dsd[K];
+  float gnorm = 0.0f;
+  RayGrads g = {};
+#pragma unroll
+  for (int i = 0; i < K; ++i) dist[i] = w[i] = dsd[i] = 0.0f;
+  if (live) {
+    float sd[K], tr[K], G[K];
+    float dep, ac;
+    backward_weights<K, L>(zz, sig, S, run, j0, nrm, dist, sd, w, tr, dep, ac);
+    g = ray_grads(r, dep, ac, g_rgb, g_disp, g_acc, g_depth);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      const int j = j0 + i;
+      G[i] = 0.0f;
+      if (i < run && j < S) {
+        // the mixed colour, kept in lone for pass 2; sum_k g_acc_objects[k] share_k in alone
+        if (cnt[i] > 1) {
+          lone[i][0] = __fdiv_rn(num[i][0], sig[i]);
+          lone[i][1] = __fdiv_rn(num[i][1], sig[i]);
+          lone[i][2] = __fdiv_rn(num[i][2], sig[i]);
+          alone[i] = aon[i] / sig[i];
+        }
+        G[i] = weight_grad(g, lone[i][0], lone[i][1], lone[i][2], zz[i], g_w ? g_w[r * S_in + j] : 0.f);
+        if (g_ao) G[i] += alone[i];
+      }
+    }
+    backward_dsd<K, L>(G, w, tr, sd, sig, dist, S, run, j0, dsd, gnorm);
+    gnorm = ray_sum<L>(gnorm);
+    if (sub == (L == 16 ? 15 : 63) && d_rd) store_d_rd(d_rd, r, gnorm, nrm, d0, d1, d2, accumulate_rd);
+  }
+
+  // pass 2: every object's d raw rows
+#pragma unroll
+  for (int k = 0; k < NOBJ; ++k) {
+    if (k >= n_objects) continue;  // uniform
+    __builtin_amdgcn_wave_barrier();  // the previous object's copy-out reads stay ahead of these stores
+    stage_rows_in<K>(reinterpret_cast<const float4*>(raws.p[k]) + rw0 * S_in, nq, sl, lane);
+    __builtin_amdgcn_wave_barrier();
+    if (live) {
+      float4 rv[K];
+      load_raw_lds<K>(sl, q0, j0, run, S_in, rv);
+#pragma unroll
+      for (int i = 0; i < K; ++i) {
+        const int j = j0 + i;
+        if (!(i < run && j < S_in)) continue;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);  // an inactive object's row, and the sample-free S_in == 1
+        const float s = j < S ? raw_sigma(rv[i].w) : 0.0f;
+        if (s != 0.0f) {
+          const float s0 = cn::sigmoid_hw(rv[i].x), s1 = cn::sigmoid_hw(rv[i].y), s2 = cn::sigmoid_hw(rv[i].z);
+          if (cnt[i] > 1) {
+            const float share = __fdiv_rn(s, sig[i]), ws = w[i] * share;
+            const float c0 = s0 * 1.002f - 0.001f, c1 = s1 * 1.002f - 0.001f, c2 = s2 * 1.002f - 0.001f;
+            o.x = colour_grad(ws, g.r0, s0);
+            o.y = colour_grad(ws, g.r1, s1);
+            o.z = colour_grad(ws, g.r2, s2);
+            // through the mixed colour and the shares: w (g_rgb . (c_k - c) + g_ao[k] - sum_j g_ao[j] share_j) / sigma
+            float mixg = g.r0 * (c0 - lone[i][0]) + g.r1 * (c1 - lone[i][1]) + g.r2 * (c2 - lone[i][2]);
+            if (g_ao) mixg += gao[k] - alone[i];
+            o.w = (dsd[i] * (dist[i] * nrm) + w[i] * mixg / sig[i]) * sigma_slope(rv[i].w);
+          } else {  // the only active object: the plain backward's row
+            o.x = colour_grad(w[i], g.r0, s0);
+            o.y = colour_grad(w[i], g.r1, s1);
+            o.z = colour_grad(w[i], g.r2, s2);
+            o.w = dsd[i] * (dist[i] * nrm) * sigma_slope(rv[i].w);
+          }
+        }
+        sl[pad4(q0 + i)] = o;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();  // the copy-out reads quads other lanes wrote
+    stage_rows_out<K>(reinterpret_cast<float4*>(d_raws.p[k]) + rw0 * S_in, nq, sl, lane);
+  }
+}
+
+template <int NOBJ>
+void launch_compose_backward(const ComposeRaws& raws, int n_objects, const float* z, const float* rd, int64_t n_rays,
+                             int S, const float* g_rgb, const float* g_disp, const float* g_acc, const float* g_w,
+                             const float* g_depth, const float* g_ao, const ComposeGrads& d_raws, float* d_rd,
+                             int accumulate_rd, hipStream_t stream) {
+  const dim3 g16(static_cast<unsigned>(cn::ceil_div(n_rays, 16))), g64(static_cast<unsigned>(cn::ceil_div(n_rays, 4)));
+#define CN_COMPOSE_BWD_LAUNCH(K, L, GRID)                                                                            \
+  hipLaunchKernelGGL((volume_render_compose_backward_kernel<K, L, NOBJ>), GRID, dim3(256), 0, stream, raws, n_objects, \
+                     z, rd, n_rays, S, g_rgb, g_disp, g_acc, g_w, g_depth, g_ao, d_raws, d_rd, accumulate_rd)
+  if (S <= 64) CN_COMPOSE_BWD_LAUNCH(4, 16, g16);
+  else if (S <= 128) CN_COMPOSE_BWD_LAUNCH(8, 16, g16);
+  else if (S <= 256) CN_COMPOSE_BWD_LAUNCH(4, 64, g64);
+  else CN_COMPOSE_BWD_LAUNCH(8, 64, g64);
+#undef CN_COMPOSE_BWD_LAUNCH
+}
+
+}  // namespace
+
+extern "C" int cn_volume_render_compose_backward(const float* const* raws, int n_objects, const float* z,
+                                                 const float* rd, int64_t n_rays, int64_t n_samples,
+                                                 const float* g_rgb, const float* g_disp, const float* g_acc,
+                                                 const float* g_weights, const float* g_depth,
+                                                 const float* g_acc_objects, float* const* d_raws, float* d_rd,
+                                                 int accumulate_rd, cn_stream_t stream) {
+  CN_CHECK_ARG(raws && d_raws && z && rd && (accumulate_rd == 0 || accumulate_rd == 1));
+  CN_CHECK_ARG(n_objects >= 1 && n_objects <= CN_MAX_SCENE_OBJECTS);
+  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && n_samples <= kMaxSamples);
+  CN_CHECK_ARG(cn::aligned16(z));
+  ComposeRaws p = {};
+  ComposeGrads d = {};
+  for (int k = 0; k < n_objects; ++k) {
+    CN_CHECK_ARG(raws[k] && cn::aligned16(raws[k]) && d_raws[k] && cn::aligned16(d_raws[k]));
+    p.p[k] = raws[k];
+    d.p[k] = d_raws[k];
+  }
+  const int s = static_cast<int>(n_samples);
+  hipStream_t st = cn::as_stream(stream);
+#define CN_COMPOSE_BWD(NOBJ)                                                                                          \
+  launch_compose_backward<NOBJ>(p, n_objects, z, rd, n_rays, s, g_rgb, g_disp, g_acc, g_weights, g_depth, g_acc_objects, \
+                                d, d_rd, accumulate_rd, st)
+  // the object count's compile-time bound, as the forward
+  if (n_objects == 1) CN_COMPOSE_BWD(1);
+  else if (n_objects == 2) CN_COMPOSE_BWD(2);
+  else if (n_objects <= 4) CN_COMPOSE_BWD(4);
+  else CN_COMPOSE_BWD(8);
+#undef CN_COMPOSE_BWD
   return cn::launch_status();
 }

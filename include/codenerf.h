@@ -895,6 +895,80 @@ int cn_posenc_backward(const float* x, int64_t m, int64_t d, const float* freqs,
 int cn_ray_points_backward(const float* g_pts, const float* z, int64_t n_rays, int64_t n_samples,
                            float* d_ro, float* d_rd, cn_stream_t stream);
 
+/* --- Scene composition, backward (fitting the poses and codes of posed objects) ---------
+ * The four backwards around the compact fields of a scene render.  All are stream-ordered on `stream`, never
+ * synchronise, use no float atomics and keep no state; argument errors return CN_EINVAL before any launch;
+ * every element of every output is written. */
+
+/* Backward of cn_volume_render_compose w.r.t. every object's raw rows and rd: the derivative of the
+ * composition rule above read as real functions, with every sample's active set (and so its active count)
+ * held fixed.  raws, z, rd and the sizes as the forward took them; g_rgb (R,3), g_disp, g_acc, g_depth (R),
+ * g_weights (R,S), g_acc_objects (K,R): the upstream gradients, each may be NULL (zero).  Per sample, with
+ * sigma_k, c_k, sigma, c and share_k as in the forward and w, T, sd, delta = dist |rd| of the integral:
+ *   G_s = dL/dw_s = g_rgb . c_s + g_depth z_s + g_acc + g_w_s + sum_k g_acc_objects[k] share_k,s;
+ *   dL/dsd_s = G_s T_s e^{-sd_s} - sum_{j>s} G_j w_j and d_rd = (sum_s dL/dsd_s sigma_s dist_s) rd / |rd|,
+ *     g_disp folded into g_depth / g_acc: cn_volume_render_backward's arithmetic on sigma and c;
+ *   with g_sigma = dL/dsd delta: an inactive object's row gets exactly (0, 0, 0, 0); the only active object a
+ *     gets d c_a = w g_rgb and d sigma_a = g_sigma; with two or more active, d c_k = w g_rgb share_k and
+ *     d sigma_k = g_sigma + sum_ch w g_rgb[ch] (c_k[ch] - c[ch]) / sigma
+ *                         + sum_j w g_acc_objects[j] ((j == k) - share_j) / sigma;
+ *   d raw_k = (d c_k 1.002 s (1 - s) per channel, s the channel's sigmoid; d sigma_k softplus20'(xs - 1), which
+ *     is 1 above the threshold 20 and the sigmoid below).
+ * With one object, or at a sample with one active object, and g_acc_objects NULL, the active row and d_rd are
+ * cn_volume_render_backward's bits.  n_samples = 1 gives zeros.
+ * d_raws: HOST array of n_objects device pointers, each (n_rays, n_samples, 4), 16-B aligned like every
+ * raws[k] and z; d_rd (R,3) may be NULL, and is added to instead of written with accumulate_rd = 1.  One launch.
+ * CN_EINVAL: raws, d_raws, an entry of either, z or rd NULL; n_objects outside 1..CN_MAX_SCENE_OBJECTS;
+ * n_rays <= 0; n_samples outside 1..512; a misaligned tensor; accumulate_rd not 0 or 1. */
+int cn_volume_render_compose_backward(const float* const* raws, int n_objects, const float* z, const float* rd,
+                                      int64_t n_rays, int64_t n_samples, const float* g_rgb, const float* g_disp,
+                                      const float* g_acc, const float* g_weights, const float* g_depth,
+                                      const float* g_acc_objects, float* const* d_raws, float* d_rd,
+                                      int accumulate_rd, cn_stream_t stream);
+
+/* Floats of cn_object_rays_backward's workspace (its blocks' partial pose sums), or -1 for sizes it refuses. */
+int64_t cn_object_rays_backward_workspace_floats(int64_t n_rays, int n_objects);
+
+/* Backward of cn_object_rays: g_ro_obj, g_rd_obj (n_objects, n_rays, 3), either may be NULL (zero); ro, rd
+ * and the HOST poses as the forward took them.  With R_k, t_k object k's rotation and translation:
+ *   d_ro[r][j] = sum_k sum_i R_k[j][i] g_ro_obj[k][r][i], d_rd the same from g_rd_obj (ascending k, then i;
+ *     one writer per element; added to the output instead with accumulate = 1);
+ *   d_poses[k] (device, 12 floats: dR row-major, then dt), written:
+ *     dR_k[j][i] = sum_r ((ro[r][j] - t_k[j]) g_ro_obj[k][r][i] + rd[r][j] g_rd_obj[k][r][i]),
+ *     dt_k[j]    = - sum_r sum_i R_k[j][i] g_ro_obj[k][r][i].
+ * The 12 sums per object are reduced in a fixed order (block partials in `workspace`, then one block per
+ * object): two runs give the same bits.  d_ro, d_rd and d_poses may each be NULL (not all three); workspace:
+ * cn_object_rays_backward_workspace_floats floats, contents on entry ignored, required with d_poses.  Two
+ * launches (one without d_poses).
+ * CN_EINVAL: ro, rd or poses NULL; no output; d_poses without a workspace; n_rays <= 0; n_objects outside
+ * 1..CN_MAX_SCENE_OBJECTS; a pose entry that is not finite; accumulate not 0 or 1. */
+int cn_object_rays_backward(const float* g_ro_obj, const float* g_rd_obj, const float* ro, const float* rd,
+                            int64_t n_rays, const float* poses, int n_objects, float* d_ro, float* d_rd,
+                            int accumulate, float* d_poses, float* workspace, cn_stream_t stream);
+
+/* Backward of cn_occupancy_expand: g_compact (M', 4) row j = g_raw (n_rays, n_samples, 4) row
+ * sample_index[j]; the gradients of culled slots are dropped (the empty row is a constant).  workspace: what
+ * the cull of the same sizes left, only read.  g_raw and g_compact 16-B aligned.  One launch.
+ * CN_EINVAL: a pointer NULL; a size cn_occupancy_cull refuses; a misaligned tensor or workspace. */
+int cn_occupancy_gather(const float* g_raw, const void* workspace, int64_t n_rays, int64_t n_samples,
+                        float* g_compact, cn_stream_t stream);
+
+/* Backward of the rows cn_occupancy_cull forms (z is not differentiated): g_pts, g_vdir (M', 3), either may be
+ * NULL (zero) -> d_ro, d_rd (n_rays, 3), either may be NULL (not both), written.  fp32, every operation rounded:
+ *   d_ro[r][i] = the sequential sum, from 0, over ray r's kept rows j in ascending order of g_pts[j][i];
+ *   d_rd[r][i] = P + V, P the sequential sum over the same rows of z[r][s_j] * g_pts[j][i] (the product rounded),
+ *     V the sequential sum of g_vdir[j][i] over the kept samples whose Q1 view-direction ray is r, in ascending
+ *     sample index: with base and rcnt of r's chunk (cn_occupancy_cull, the same chunk_rows) these are the
+ *     chunk's samples (r - base) + i rcnt, i = 0 .. n_samples - 1, sample k' being sample k' % n_samples of ray
+ *     base + k' / n_samples.
+ * A gather: one writer per element, a ray with nothing kept gets zeros.  workspace as cn_occupancy_gather.
+ * One launch.
+ * CN_EINVAL: z or workspace NULL; no output; a size cn_occupancy_cull refuses; chunk_rows <= 0; workspace not
+ * 8-byte aligned. */
+int cn_occupancy_cull_backward(const float* g_pts, const float* g_vdir, const float* z, const void* workspace,
+                               int64_t n_rays, int64_t n_samples, int64_t chunk_rows, float* d_ro, float* d_rd,
+                               cn_stream_t stream);
+
 /* --- The step's scalar loss (train.py:103-108, eval.py:157-163) ---------------
  * out[6] = [mse(rgb_coarse, target[:, :3]), mse(rgb_fine, target[:, :3]),
  *           lambda * (||z_s|| + ||z_t||), their sum, ||z_s||, ||z_t||] (fp32, device), with
