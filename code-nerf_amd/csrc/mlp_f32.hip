@@ -240,7 +240,8 @@ struct State {
   floatx4 acc[16];   // layer output accumulators
   floatx4 pre[4];    // the next chunk's first A fragments (read during this chunk's last k-step)
   floatx4 acc2[4];   // backward: the narrow chunks' accumulators (2 blocks x 2 chains)
-  floatx4 row[12];   // folded table variant: the view-direction row's first blocks on their way to the accumulators
+  floatx4 row[12];   // folded table variant: the view-direction row's first blocks on their way to the accumulators;
+                     // between layer_dir2 and the next tile's head, blocks 0..2 carry that tile's inputs (prefetch_rows)
   float denc[8];     // view-direction encoding, k-steps of the view-dir chunk
   float sig;         // sigma partial (this lane group's 64 features)
   int lane, g, wave;
@@ -366,6 +367,26 @@ __device__ __forceinline__ void dma_chunk(const State& s, float4* lds, int cn) {
 
 // M_c: chunk c+1 landed for every wave (all but this wave's 4 youngest DMA pieces --
 // chunk c+2's -- retired), every wave past chunk c-1, this wave's LDS reads returned.
+//
+// The folded table variant (kStreamRows) issues chunk c+3's pieces one per k-step in k-steps 4..7 of chunk
+// c, behind each k-step's MFMAs, instead of all four right after M_c, where all 8 waves -- both waves of
+// every SIMD -- stood in the same issue stall.  The count is unchanged and the same for every wave; what
+// each wave has outstanding at M_c, oldest first, and what vmcnt(4) makes of it:
+//
+//   issued                                   in              at M_c
+//   chunk c+1, pieces 0..3                   chunk c-2, k-steps 4..7    retired (waited for)
+//   ordinary loads of chunk c-2 / c-1 (*)    behind their k-step        retired (waited for: more than needed)
+//   chunk c+2, pieces 0..3                   chunk c-1, k-steps 4..7    may fly: the 4 youngest
+//   the tile's raw store (+)                 after the rgb chunk        youngest at the next tile's first
+//                                                                       barrier: one piece more is waited for
+//   (*) RowLoads' 12 row blocks (layer_xyz2, chunk 6, k-step 4: between pieces 0 and 1) and prefetch_rows'
+//       loads (layer_dir2, chunk 2, right behind its barrier: before piece 0); the row's last 4 blocks are
+//       waited for with vmcnt(0) before the folded layer's first chunk.
+//   (+) 9 outstanding there; at most 4 remain, so 5 retired, at most one of them the store: the 4 oldest
+//       loads, chunk c+1's, have retired whether or not the store keeps its place among them.
+// No piece of chunk c+3 targets a slot in use: its slot is chunk c-1's, whose last read precedes M_c in
+// every wave, and the pieces follow M_c.  The tile head waits for nothing; the trailing vmcnt(0) before
+// the workgroup ends stays.
 __device__ __forceinline__ void chunk_barrier() {
   asm volatile("s_waitcnt vmcnt(4)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
@@ -432,6 +453,7 @@ struct NoPost {
 // barrier's counted vmcnt still sees the ring's pieces in order.
 template <int NS, int CI = 0, int NG = kStreamFull, typename GetB, typename Post = NoPost>
 __device__ __forceinline__ void chunk16(State& s, float4* lds, int c, GetB getb, Post post = Post{}) {
+  static_assert(NG != kStreamRows || NS == 8, "the table variant's pieces ride in k-steps 4..7 of a full chunk");
   const float4* slot = lds + (c & (kRing - 1)) * kChunkQuads + s.lane;
   const float4* nslot = lds + ((c + 1) & (kRing - 1)) * kChunkQuads + s.lane;
   floatx4 a0[4], a1[4];
@@ -450,8 +472,10 @@ __device__ __forceinline__ void chunk16(State& s, float4* lds, int c, GetB getb,
     if constexpr ((T) == 3) {                                       \
       chunk_barrier();                                              \
       post.template before_dma<CI>();                               \
-      dma_chunk<NG>(s, lds, c + 3);                                 \
+      if constexpr (NG != kStreamRows) dma_chunk<NG>(s, lds, c + 3); \
     }                                                               \
+    if constexpr (NG == kStreamRows && (T) >= 4)                    \
+      dma_piece<NG>(s, lds, c + 3, (T) - 4);                        \
     post.template step<CI, (T)>();                                  \
   }
   CN_STEP(0, a0, a1)
@@ -712,11 +736,25 @@ struct XencStore {
 // barrier's counted vmcnt then waits for them too, which only asks more than it needs), so they fly
 // under a chunk and a half of MFMAs -- all 8 waves of a tile meet every chunk barrier together, and a
 // load waited for between two chunks stalls both waves of every SIMD at once.
+//
+// The next tile's per-sample inputs travel the same way (prefetch_rows), right behind the third chunk
+// barrier of layer_dir2, where s.row's registers are free: the tile head then waits for no load.
 constexpr int kRowEarly = 12;
+template <int MODE>
+__device__ __forceinline__ void prefetch_rows(State& s, const FieldArgs& a, int64_t tile);
+template <int MODE>
 struct RowLoads {
   State& s;
+  const FieldArgs& a;
   const float* row;  // this lane's table row
   bool on;           // the layer is layer_xyz2
+  int64_t next;      // layer_dir2: the workgroup's next tile (< 0 in the other layers)
+  template <int CI>
+  __device__ __forceinline__ void before_dma() const {
+    if constexpr (CI == 2) {
+      if (next >= 0) prefetch_rows<MODE>(s, a, next);
+    }
+  }
   template <int CI, int T>
   __device__ __forceinline__ void step() const {
     if constexpr (CI == 6 && T == 4) {
@@ -727,8 +765,6 @@ struct RowLoads {
       }
     }
   }
-  template <int CI>
-  __device__ __forceinline__ void before_dma() const {}
 };
 
 // sigma = fc_out row 0 . [h2, zs2] + b: the h2 part (s.act = h2, this lane group's 64 features), the
@@ -787,6 +823,45 @@ __device__ __forceinline__ SampleIn decode_sample_rows(const FieldArgs& a, int64
   }
 }
 
+// decode_sample_rows' loads and index arithmetic for a tile that exists (rows past m clamp to the last
+// row, as field_tile's), without the point's arithmetic, into s.row's first blocks, which are free from
+// layer_dir1's start to the next tile's layer_xyz2: rd, z | ro (or the point) | the Q1 direction ray.
+template <int MODE>
+__device__ __forceinline__ void prefetch_rows(State& s, const FieldArgs& a, int64_t tile) {
+  static_assert(MODE != kFromEncoded, "geometry modes");
+  const int64_t row = tile * kTile + s.wave * 16 + (s.lane & 15);
+  const int64_t rc = row < a.m ? row : a.m - 1;
+  const int64_t S = a.n_samples;
+  const int64_t ray = rc / S, smp = rc - ray * S;
+  // (each load lands in its place: a value assembled from several loads would be waited for here)
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    if constexpr (MODE == kFromPts) {
+      s.row[1][j] = a.pts[3 * rc + j];
+    } else {
+      s.row[0][j] = a.rd[3 * ray + j];
+      s.row[1][j] = a.ro[3 * ray + j];
+    }
+  }
+  if constexpr (MODE == kFromRayZ) s.row[0][3] = a.z[rc];
+  const int64_t base = (ray / a.chunk_rows) * a.chunk_rows;
+  const int64_t rcnt = min(a.chunk_rows, a.n_rays - base);
+  const uint64_t dray = static_cast<uint64_t>(base + ((ray - base) * S + smp) % rcnt);
+  s.row[2][0] = __uint_as_float(static_cast<unsigned>(dray));
+  s.row[2][1] = __uint_as_float(static_cast<unsigned>(dray >> 32));
+}
+// The point of the tile prefetch_rows loaded (decode_sample_rows' arithmetic).
+template <int MODE>
+__device__ __forceinline__ void prefetched_point(const State& s, float (&x)[3], int64_t& dray) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    if constexpr (MODE == kFromPts) x[j] = s.row[1][j];
+    else x[j] = mul_add_rn(s.row[0][j], s.row[0][3], s.row[1][j]);
+  }
+  dray = static_cast<int64_t>(static_cast<uint64_t>(__float_as_uint(s.row[2][0])) |
+                              static_cast<uint64_t>(__float_as_uint(s.row[2][1])) << 32);
+}
+
 // The view-direction encoding's evaluator for one lane: fast_sincosf when this direction's largest
 // argument is in its range, ocml's sincosf otherwise.  It depends on the direction and the largest
 // |frequency| alone, so a finite direction's encoding -- and its row of the table -- has the same
@@ -820,14 +895,16 @@ __device__ __forceinline__ void view_dir_enc(const float (&vd)[3], const float (
 // plus the view-direction chunk's product, a function of the Q1 direction ray alone -- comes from the
 // per-ray table a.view_rows (view_rows_kernel, the same MFMAs over the same operands: the same bits).
 // The tile then decodes no direction, evaluates no view-direction encoding and streams the pack
-// without chunk kFDir (kStreamRows: 27 chunks, the counter c runs on across tiles from s.cbase).
+// without chunk kFDir (kStreamRows: 27 chunks, the counter c runs on across tiles from s.cbase).  The one
+// code row is staged before the tile loop and the next tile's inputs are loaded during layer_dir2
+// (prefetch_rows), so the tile head issues no load and waits for none.
 // Most of the 16 row loads are issued inside layer_xyz2 (RowLoads) into registers of their own and
 // move to the accumulators once relu(h2) has left them; the rest are issued then, ahead of
 // sigma_partial, and waited for with vmcnt(0) after it (the ring's pieces in flight before them retire
 // first, so the next barrier's counted vmcnt still holds).
 template <int MODE, bool MASKS, bool SAVE = false, bool FOLD = false, bool ROWS = false>
 __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4* lds, float* clds, float* crow_lds,
-                                          int64_t tile, int& c) {
+                                          int64_t tile, int& c, int64_t next = -1) {
   static_assert(!FOLD || (!MASKS && !SAVE), "the folded kernel has no feat plane and no fc_out input gradient");
   static_assert(!ROWS || (FOLD && MODE != kFromEncoded), "the table variant is a folded kernel on geometry");
   constexpr int NG = ROWS ? kStreamRows : (FOLD ? kStreamFold : kStreamFull);
@@ -837,13 +914,23 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
   if constexpr (ROWS) s.cbase = c;
 
   // ---- per-sample inputs, code row (ordinary loads: the in-flight DMA retires with them)
+  // ROWS: the inputs were loaded during the tile before (prefetch_rows; the kernel's prologue for a
+  // workgroup's first tile) and the one code row was staged before the tile loop: no load, no wait.
   int64_t dray = 0;  // ROWS: the Q1 direction ray, the table row
-  const SampleIn in = ROWS ? decode_sample_rows<MODE>(a, rc, dray) : decode_sample<MODE>(a, rc);
-  s.crow = static_cast<int>(code_row(a, in.code_of));
-  const int crow0 = __builtin_amdgcn_readfirstlane(s.crow);
-  s.uniform_code = __builtin_amdgcn_readfirstlane(__ballot(s.crow != crow0) == 0 ? 1 : 0) != 0;
+  SampleIn in;
   float cbr[9];
-  {
+  if constexpr (ROWS) {
+    prefetched_point<MODE>(s, in.x, dray);
+    in.vd[0] = in.vd[1] = in.vd[2] = 0.0f;
+    in.nrm = 0.0f;
+    in.code_of = 0;
+    s.crow = 0;
+    s.uniform_code = true;
+  } else {
+    in = decode_sample<MODE>(a, rc);
+    s.crow = static_cast<int>(code_row(a, in.code_of));
+    const int crow0 = __builtin_amdgcn_readfirstlane(s.crow);
+    s.uniform_code = __builtin_amdgcn_readfirstlane(__ballot(s.crow != crow0) == 0 ? 1 : 0) != 0;
     const float* src = a.code_bias + (int64_t)crow0 * kCbStride;
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
@@ -866,11 +953,13 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
       s.denc[t] = col >= 0 ? xr[kDimXyz + col] : 0.0f;
     }
   }
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+  if constexpr (!ROWS) {
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
 #pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const int j = s.lane + 64 * k;
-    if (j < kCbStride) crow_lds[j] = cbr[k];
+    for (int k = 0; k < 9; ++k) {
+      const int j = s.lane + 64 * k;
+      if (j < kCbStride) crow_lds[j] = cbr[k];
+    }
   }
 
   // ---- encodings (lane group g owns pairs p = 4 i + g) and layer_xyz1 (63 -> 256): 2 chunks of
@@ -997,15 +1086,21 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
     else if (layer == kOut) bias_code(s, a, crow_lds, kCbFeat);
     else bias_from(s, clds + (layer == kDir1 ? kCBD1 : kCBD2));
     __builtin_amdgcn_sched_barrier(0);
-    if (FOLD && !ROWS && layer == kOut) {
-      chunk16<7, 0, NG>(s, lds, c, ArrB<0>{s.denc});
-      c += 1;
+    if constexpr (FOLD && !ROWS) {
+      if (layer == kOut) {
+        chunk16<7, 0, NG>(s, lds, c, ArrB<0>{s.denc});
+        c += 1;
+      }
     }
-    if constexpr (ROWS) layer256<NG>(s, lds, c, RowLoads{s, a.view_rows + dray * kHidden, layer == kXyz2});
+    if constexpr (ROWS)
+      layer256<NG>(s, lds, c,
+                   RowLoads<MODE>{s, a, a.view_rows + dray * kHidden, layer == kXyz2, layer == kDir2 ? next : -1});
     else layer256<NG>(s, lds, c, st);
-    if (!FOLD && layer == kDir1) {
-      chunk16<7, 0, NG>(s, lds, c, ArrB<0>{s.denc});
-      c += 1;
+    if constexpr (!FOLD) {
+      if (layer == kDir1) {
+        chunk16<7, 0, NG>(s, lds, c, ArrB<0>{s.denc});
+        c += 1;
+      }
     }
   }
 
@@ -1108,6 +1203,17 @@ __global__ __launch_bounds__(kThreads, 2) void field_w16_kernel(FieldArgs a) {
   float* crow_lds = clds + kLdsConsts + s.wave * kCbStride;
 
   load_consts(a, clds, FOLD ? kFoldStreamFloats : kStreamFloats);
+  if constexpr (ROWS) {
+    // one code row and no code_index (launch_field_w16_fold_rows): each wave stages its copy once (c_v1's
+    // slot stays unwritten: the table rows hold it), and the first tile's inputs are loaded here
+    const float* src = a.code_bias;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const int j = s.lane + 64 * k;
+      if (j < kCbStride && !(j >= kCbFeat && j < kCbSigma)) crow_lds[j] = src[j];
+    }
+    prefetch_rows<MODE>(s, a, blockIdx.x);
+  }
   // prime the ring with chunks 0..2, wait for chunk 0 everywhere, read its first fragments
   dma_chunk<NG>(s, lds, 0);
   dma_chunk<NG>(s, lds, 1);
@@ -1122,10 +1228,12 @@ __global__ __launch_bounds__(kThreads, 2) void field_w16_kernel(FieldArgs a) {
     if constexpr (ROWS) {
       // 27 chunks per tile: the counter runs on (ring slot c & 3), folded mod lcm(27, ring)
       if (c >= 4 * kRowsChunks) c -= 4 * kRowsChunks;
+      const int64_t next = tile + gridDim.x;
+      field_tile<MODE, MASKS, SAVE, FOLD, ROWS>(s, a, lds, clds, crow_lds, tile, c, next < n_tiles ? next : -1);
     } else {
       c = 0;
+      field_tile<MODE, MASKS, SAVE, FOLD, ROWS>(s, a, lds, clds, crow_lds, tile, c);
     }
-    field_tile<MODE, MASKS, SAVE, FOLD, ROWS>(s, a, lds, clds, crow_lds, tile, c);
   }
   // the last tile prefetched chunks 0..2 of a tile that does not exist: they must land
   // before the workgroup's LDS is released
