@@ -116,6 +116,8 @@ SIGNATURES = {
     "cn_occupancy_cull_workspace_bytes": (_i64, [_i64, _i64]),
     "cn_occupancy_cull": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _f, _f, _p, _p, _p, _p, _p, _p, _p]),
     "cn_occupancy_expand": (_i, [_p, _p, _i64, _i64, _p, _p]),
+    "cn_sample_span": (_i, [_p, _p, _i64, ctypes.POINTER(_p), ctypes.POINTER(_i64), _fp, _fp, _i, _f, _f, _i64, _i64,
+                            _p, _p, _p, _p, _p]),
     "cn_weight_cull": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _f, ctypes.c_double, _p, _p, _p, _p, _p, _p, _p]),
     "cn_scatter_rgb": (_i, [_p, _p, _i64, _p, _i64, _p]),
     "cn_volume_render_compose": (_i, [ctypes.POINTER(_p), _i, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p]),

@@ -483,7 +483,8 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
                 t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
                 coarse_only: bool = False, events: Optional[dict] = None,
                 coarse_rgb: bool = True, occupancy: Optional[OccupancyGrid] = None,
-                rgb_tolerance: Optional[float] = None, normals: bool = False) -> Dict[str, torch.Tensor]:
+                rgb_tolerance: Optional[float] = None, normals: bool = False,
+                span_probes: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """predict_radiance_and_render over a whole ray list, chunk semantics kept via ``chunk_rows``.
 
     Returns rgb/depth/acc for the coarse pass (+ weights) and, unless
@@ -515,7 +516,19 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     length is at most "acc_fine".  A sample of weight exactly 0 -- every culled one -- contributes 0 even
     where its normal is NaN.  Every other entry is bitwise the call's without ``normals``; composes with
     ``occupancy`` and ``rgb_tolerance`` (the gradient kernel still runs over every fine sample).
+    ``span_probes`` (needs ``occupancy`` and a sampler linear in depth, spacing_mode "lindisp"): a probe count,
+    a multiple of 64 in [64, 1024].  The coarse depths then come from PointSampler.sample_span in place of
+    sample_uniform: each ray's Nc depths are stratified inside its own span of the sampler's [near, far], from
+    the probe before its first occupied cell to the probe after its last (include/codenerf.h's rule), with
+    ``t_rand`` as before; a ray that meets no occupied cell keeps the whole range.  Everything after the coarse
+    depths is the same code path.  Adds "ray_span" (R, 2), the rays' (t_lo, t_hi), and "ray_hit" (R,) bool.
+    The span is not strictly conservative (a corner clipped between two probes), which a grid dilated by one
+    cell -- OccupancyGrid.from_density's default -- covers.
     """
+    if span_probes is not None:
+        if occupancy is None:
+            raise ValueError("span_probes places the coarse samples by the occupancy grid: pass occupancy=")
+        point_sampler.check_span_probes(span_probes)
     if normals and (coarse_only or fine_model is None):
         raise ValueError("normals=True composites the fine pass's normals: there is no fine pass with "
                          "coarse_only=True (or without a fine model)")
@@ -558,8 +571,11 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     ps = point_sampler
     if ps.perturb and t_rand is None:
         t_rand = torch.rand(n, ps.num_samples_coarse, dtype=torch.float32, device=ro.device)
-    _, z_c = ops.sample_uniform(ro.detach(), rd.detach(), ps.z_vals, ps.lower, ps.upper,
-                                t_rand if ps.perturb else None, want_pts=False)
+    if span_probes is None:
+        _, z_c = ops.sample_uniform(ro.detach(), rd.detach(), ps.z_vals, ps.lower, ps.upper,
+                                    t_rand if ps.perturb else None, want_pts=False)
+    else:
+        z_c, ray_span, probe_range = ps.sample_span(ro, rd, occupancy, t_rand, span_probes)
     pair = None
     if occupancy is not None:
         def culled(density_only):
@@ -591,6 +607,8 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
            "depth_coarse": depth_c, "z_coarse": z_c}
     if not coarse_rgb:
         del out["rgb_coarse"]       # composited from zero colours: not a result
+    if span_probes is not None:
+        out.update({"ray_span": ray_span, "ray_hit": probe_range[:, 0] >= 0})
     if coarse_only:
         return out
     if ps.perturb and u is None:
@@ -645,7 +663,8 @@ class SceneObject:
 
 def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: PointSampler, embedders, coarse_model,
                  fine_model=None, *, coarse_only: bool = False, coarse_rgb: bool = True,
-                 t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                 t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
+                 span_probes: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """Several posed objects (1..8 SceneObjects) in one image: render_rays' hierarchical render of the world
     rays ``ro`` / ``rd`` (R, 3), with the objects composed per sample.  A rigid pose keeps the ray
     parameter, so one set of depths along the world ray serves every object: the coarse depths
@@ -658,6 +677,9 @@ def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: Poi
     of "acc_*", its instance mask.  A sample's view direction is its own ray's (``chunk_rows`` is the whole
     ray list).  With one identity-posed object every shared entry is bitwise
     render_rays(..., occupancy=grid, chunk_rows=None)'s.
+    ``span_probes``: render_rays' argument.  A ray's span is that of the union of the objects' occupied probes
+    (each object's grid probed along its own object-frame ray), so the shared coarse depths cover every object the
+    ray meets; adds "ray_span" and "ray_hit".
     Inference only.  Each object's kept count is read back once per field call -- 2 K host
     synchronisations per render (K with ``coarse_only``) -- so this render is not graph-capturable."""
     objects = list(objects)
@@ -673,14 +695,20 @@ def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: Poi
                 for p in _unwrap(m).param_list())):
         raise ValueError("render_scene is an inference render: the compacted fields and the composition have no "
                          "backward (render under torch.no_grad())")
+    if span_probes is not None:
+        point_sampler.check_span_probes(span_probes)
     n = ro.shape[0]
     ps = point_sampler
     with torch.no_grad():
         if ps.perturb and t_rand is None:
             t_rand = torch.rand(n, ps.num_samples_coarse, dtype=torch.float32, device=ro.device)
-        _, z_c = ops.sample_uniform(ro, rd, ps.z_vals, ps.lower, ps.upper, t_rand if ps.perturb else None,
-                                    want_pts=False)
+        if span_probes is None:
+            _, z_c = ops.sample_uniform(ro, rd, ps.z_vals, ps.lower, ps.upper, t_rand if ps.perturb else None,
+                                        want_pts=False)
         ro_k, rd_k = ops.object_rays(ro, rd, [(o.rotation, o.translation) for o in objects])
+        if span_probes is not None:
+            z_c, ray_span, probe_range = ps.sample_span(ro_k, rd_k, [o.occupancy for o in objects], t_rand,
+                                                        span_probes)
 
         def fields(models, z, density_only):
             return [_culled_field(m, embedders, rd_k[k], o.z_s, o.z_t, n, ro_k[k], z, o.occupancy, density_only)
@@ -692,6 +720,8 @@ def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: Poi
                "depth_coarse": depth_c, "z_coarse": z_c, "acc_objects_coarse": obj_c}
         if not coarse_rgb:
             del out["rgb_coarse"]       # composited from zero colours: not a result
+        if span_probes is not None:
+            out.update({"ray_span": ray_span, "ray_hit": probe_range[:, 0] >= 0})
         if coarse_only:
             return out
         if ps.perturb and u is None:
@@ -803,7 +833,8 @@ def predict_radiance_and_render(rays: Tuple[torch.Tensor, torch.Tensor], point_s
 def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, samplers, embedders, device,
                           key: str = "rgb_fine", coarse_only: bool = False,
                           coarse_rgb: bool = True, occupancy: Optional[OccupancyGrid] = None,
-                          rgb_tolerance: Optional[float] = None) -> Optional[torch.Tensor]:
+                          rgb_tolerance: Optional[float] = None,
+                          span_probes: Optional[int] = None) -> Optional[torch.Tensor]:
     """nerf/__init__.py:137-226: shard the image's rays over ranks, render, gather on rank 0.
 
     The split is the reference's (Q5: truncating, the last rank takes the
@@ -814,6 +845,7 @@ def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, sam
     ``coarse_rgb=False``: the coarse pass computes densities only (render_rays); ``key`` cannot then
     be "rgb_coarse".  ``occupancy``: an OccupancyGrid of the object, for render_rays' sample culling.
     ``rgb_tolerance``: render_rays' bound for the fine pass's weight-based colour culling.
+    ``span_probes``: render_rays' probe count for per-ray coarse depth spans (needs ``occupancy``).
     """
     if not coarse_rgb and key == "rgb_coarse":
         raise ValueError('coarse_rgb=False renders no coarse colours: key="rgb_coarse" needs coarse_rgb=True')
@@ -838,7 +870,7 @@ def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, sam
         out = render_rays(ro[sl].to(device), rd[sl].to(device), z_s, z_t, point_sampler, embedders,
                           models["nerf_coarse"], models.get("nerf_fine"), cfg.nerf.validation.chunksize,
                           coarse_only=coarse_only, coarse_rgb=coarse_rgb, occupancy=occupancy,
-                          rgb_tolerance=rgb_tolerance)
+                          rgb_tolerance=rgb_tolerance, span_probes=span_probes)
         rgb = out[key]
         if not is_distributed:
             return rgb

@@ -787,6 +787,70 @@ def occupancy_expand(raw_compact: Optional[Tensor], state) -> Tensor:
     return raw
 
 
+def _grid_triples(grids) -> list:
+    """``grids`` as a list of (bits, resolution, bound): one grid or a sequence of them, each a triple or an
+    object with those attributes (nerf.OccupancyGrid)."""
+    def one(g):
+        if hasattr(g, "bits"):
+            return g.bits, g.resolution, g.bound
+        return tuple(g)
+    if hasattr(grids, "bits") or (isinstance(grids, (tuple, list)) and len(grids) == 3
+                                  and isinstance(grids[0], torch.Tensor)):
+        return [one(grids)]
+    return [one(g) for g in grids]
+
+
+def sample_span(ro: Tensor, rd: Tensor, grids, near: float, far: float, n_probes: int, nc: int,
+                t_rand: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Per-ray depth spans from occupancy grids and the coarse depths stratified inside them (cn_sample_span;
+    the rule is in include/codenerf.h) -> z (R, Nc), span (R, 2) = (t_lo, t_hi), probe_range (R, 2) int32 =
+    (first, last) occupied probe, (-1, -1) for a ray that meets no occupied cell (it keeps [near, far]).
+    ``ro`` / ``rd``: (R, 3) for one grid, or (K, R, 3) for K grids, each object's rays in its own frame
+    (object_rays).  ``grids``: one grid or K of them, each (bits, resolution, bound) or an object with those
+    attributes.  ``n_probes``: a multiple of 64 in [64, 1024]; ``nc`` in [2, 512]; ``t_rand`` (R, Nc) as
+    sample_uniform's (its last column is not read).  One launch, graph-capturable."""
+    lib = _lib_ready()
+    ro, rd = _cuda(ro, "ro"), _cuda(rd, "rd")
+    triples = _grid_triples(grids)
+    k = len(triples)
+    assert 1 <= k <= _lib.CN_MAX_SCENE_OBJECTS, f"a scene holds 1..{_lib.CN_MAX_SCENE_OBJECTS} objects, got {k}"
+    if ro.dim() == 2:
+        assert k == 1, "ro / rd (num_rays, 3) go with one grid: K grids take (K, num_rays, 3)"
+        ro, rd = ro.unsqueeze(0), rd.unsqueeze(0)
+    n = ro.shape[1]
+    assert ro.shape == (k, n, 3) and rd.shape == (k, n, 3), "ro / rd must be (num_grids, num_rays, 3)"
+    n_probes, nc, near, far = int(n_probes), int(nc), float(near), float(far)
+    assert n_probes % 64 == 0 and 64 <= n_probes <= 1024, "n_probes must be a multiple of 64 in [64, 1024]"
+    assert 2 <= nc <= 512, "nc must be in [2, 512]"
+    assert 0.0 <= near < far < float("inf"), "near / far must be finite with 0 <= near < far"
+    bits_list, res, lo, inv = [], [], [], []
+    for j, (bits, resolution, bound) in enumerate(triples):
+        bits = _cuda(bits, f"grids[{j}].bits", torch.int32)
+        g = int(resolution)
+        assert g % 32 == 0 and 32 <= g <= 512 and bits.shape == (g * g * g // 32,), \
+            "bits must be the (G^3 / 32,) words of a grid of resolution G, a multiple of 32 in [32, 512]"
+        assert float(bound) > 0.0 and float(bound) < float("inf"), "a grid's bound must be positive and finite"
+        l, i = _grid_scale(g, bound)
+        bits_list.append(bits)
+        res.append(g)
+        lo.append(l)
+        inv.append(i)
+    if t_rand is not None:
+        t_rand = _cuda(t_rand, "t_rand")
+        assert t_rand.shape == (n, nc), "t_rand must be (num_rays, num_coarse)"
+    dev = ro.device
+    z = torch.empty(n, nc, device=dev, dtype=torch.float32)
+    span = torch.empty(n, 2, device=dev, dtype=torch.float32)
+    probe_range = torch.empty(n, 2, device=dev, dtype=torch.int32)
+    if n:
+        pointers, keep = _lib.pointer_array(bits_list)
+        check(lib.cn_sample_span(ptr(ro), ptr(rd), n, pointers, (ctypes.c_int64 * k)(*res), _lib.host_floats(lo),
+                                 _lib.host_floats(inv), k, near, far, n_probes, nc, ptr(t_rand), ptr(z), ptr(span),
+                                 ptr(probe_range), stream_of(z)), "cn_sample_span")
+        del keep
+    return z, span, probe_range
+
+
 # ------------------------------------------------------------------ iso-surface extraction
 
 

@@ -48,6 +48,26 @@ __device__ __forceinline__ float mul_add_rn(float a, float b, float c) {
   return __fadd_rn(__fmul_rn(a, b), c);
 }
 
+// An occupancy grid's resolution: a multiple of 32 in [32, 512] (include/codenerf.h).
+inline bool grid_ok(int64_t g) { return g >= 32 && g <= 512 && g % 32 == 0; }
+
+// The occupancy lookup of include/codenerf.h: u_d = (p_d - lo) inv_cell, each op rounded; inside iff
+// 0 <= u_d < G on every axis (false for NaN), cell floor(u_d).
+__device__ __forceinline__ bool occupied(const unsigned* __restrict__ bits, int g, float lo, float inv_cell,
+                                         float p0, float p1, float p2) {
+  const float u0 = __fmul_rn(__fsub_rn(p0, lo), inv_cell);
+  const float u1 = __fmul_rn(__fsub_rn(p1, lo), inv_cell);
+  const float u2 = __fmul_rn(__fsub_rn(p2, lo), inv_cell);
+  const float gf = static_cast<float>(g);
+  const bool inside = u0 >= 0.0f && u0 < gf && u1 >= 0.0f && u1 < gf && u2 >= 0.0f && u2 < gf;
+  if (!inside) return false;
+  const unsigned i0 = static_cast<unsigned>(static_cast<int>(floorf(u0)));
+  const unsigned i1 = static_cast<unsigned>(static_cast<int>(floorf(u1)));
+  const unsigned i2 = static_cast<unsigned>(static_cast<int>(floorf(u2)));
+  const unsigned c = (i0 * g + i1) * g + i2;      // < G^3 <= 2^27
+  return (bits[c >> 5] >> (c & 31)) & 1u;
+}
+
 // torch.nn.functional.softplus(x) with beta 1, threshold 20 (volumetric_render.py:32):
 // log1p(e), e = expf(x), as log(u) + (e - (u - 1)) / u with u = fl(1 + e) -- the rounding of u
 // compensated to first order -- on the hardware log2 (v_log_f32) instead of the libm log1pf, whose

@@ -36,8 +36,6 @@ inline bool sizes_ok(int64_t n_rays, int64_t n_samples) {
   return n_rays > 0 && n_samples >= 1 && n_samples <= kMaxSamples && n_rays <= INT_MAX / n_samples;
 }
 
-inline bool grid_ok(int64_t g) { return g >= 32 && g <= 512 && g % 32 == 0; }
-
 // Lanes of this wave below the caller's whose bit is set in m.
 __device__ __forceinline__ int rank_below(unsigned long long m) {
   return static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(m >> 32),
@@ -69,23 +67,6 @@ __global__ __launch_bounds__(256) void occupancy_build_kernel(const float* __res
   if ((lane & 31) == 0) bits[c >> 5] = static_cast<unsigned>(b >> lane);
 }
 
-// The lookup of include/codenerf.h: u_d = (p_d - lo) inv_cell, each op rounded; inside iff
-// 0 <= u_d < G on every axis (false for NaN), cell floor(u_d).
-__device__ __forceinline__ bool occupied(const unsigned* __restrict__ bits, int g, float lo, float inv_cell,
-                                         float p0, float p1, float p2) {
-  const float u0 = __fmul_rn(__fsub_rn(p0, lo), inv_cell);
-  const float u1 = __fmul_rn(__fsub_rn(p1, lo), inv_cell);
-  const float u2 = __fmul_rn(__fsub_rn(p2, lo), inv_cell);
-  const float gf = static_cast<float>(g);
-  const bool inside = u0 >= 0.0f && u0 < gf && u1 >= 0.0f && u1 < gf && u2 >= 0.0f && u2 < gf;
-  if (!inside) return false;
-  const unsigned i0 = static_cast<unsigned>(static_cast<int>(floorf(u0)));
-  const unsigned i1 = static_cast<unsigned>(static_cast<int>(floorf(u1)));
-  const unsigned i2 = static_cast<unsigned>(static_cast<int>(floorf(u2)));
-  const unsigned c = (i0 * g + i1) * g + i2;      // < G^3 <= 2^27
-  return (bits[c >> 5] >> (c & 31)) & 1u;
-}
-
 // Pass 1, one wave per ray: the kept mask of each 64 samples (a ballot) and the ray's kept count.
 __global__ __launch_bounds__(64 * kRayWaves) void occupancy_mask_kernel(
     const float* __restrict__ ro, const float* __restrict__ rd, const float* __restrict__ z, int64_t n_rays, int n_samples,
@@ -103,7 +84,7 @@ __global__ __launch_bounds__(64 * kRayWaves) void occupancy_mask_kernel(
     bool keep = false;
     if (s < n_samples) {
       const float zv = z[r * n_samples + s];
-      keep = occupied(bits, g, lo, inv_cell, cn::mul_add_rn(d0, zv, o0), cn::mul_add_rn(d1, zv, o1),
+      keep = cn::occupied(bits, g, lo, inv_cell, cn::mul_add_rn(d0, zv, o0), cn::mul_add_rn(d1, zv, o1),
                       cn::mul_add_rn(d2, zv, o2));
     }
     const unsigned long long m = __ballot(keep);
@@ -301,7 +282,7 @@ extern "C" int64_t cn_occupancy_cull_workspace_bytes(int64_t n_rays, int64_t n_s
 
 extern "C" int cn_occupancy_build(const float* nodes, int64_t g, float threshold, int dilate, uint32_t* bits,
                                   cn_stream_t stream) {
-  CN_CHECK_ARG(nodes && bits && grid_ok(g) && dilate >= 0 && dilate <= 2);
+  CN_CHECK_ARG(nodes && bits && cn::grid_ok(g) && dilate >= 0 && dilate <= 2);
   const unsigned blocks = static_cast<unsigned>(g * g * g / 256);      // g % 32 == 0: exact
   hipLaunchKernelGGL(occupancy_build_kernel, dim3(blocks), dim3(256), 0, cn::as_stream(stream), nodes,
                      static_cast<int>(g), threshold, dilate, bits);
@@ -312,7 +293,7 @@ extern "C" int cn_occupancy_cull(const float* ro, const float* rd, const float* 
                                  int64_t chunk_rows, const int64_t* code_index, const uint32_t* bits, int64_t g,
                                  float lo, float inv_cell, void* workspace, int64_t* count, int32_t* sample_index,
                                  float* pts, float* vdir, int64_t* code_out, cn_stream_t stream) {
-  CN_CHECK_ARG(bits && grid_ok(g));
+  CN_CHECK_ARG(bits && cn::grid_ok(g));
   CN_CHECK_ARG(cull_args_ok(ro, rd, z, n_rays, n_samples, chunk_rows, workspace, count, sample_index, pts, vdir));
   hipStream_t st = cn::as_stream(stream);
   hipLaunchKernelGGL(occupancy_mask_kernel, dim3(static_cast<unsigned>(cn::ceil_div(n_rays, kRayWaves))),

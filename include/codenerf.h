@@ -429,6 +429,47 @@ int cn_occupancy_cull(const float* ro, const float* rd, const float* z, int64_t 
 int cn_occupancy_expand(const float* raw_compact, const void* workspace, int64_t n_rays, int64_t n_samples,
                         float* raw, cn_stream_t stream);
 
+/* --- Per-ray depth spans (inference) -------------------------------------
+ * Where the coarse samples go: each ray gets its own depth interval, from just before its first
+ * occupied grid cell to just after its last, and its nc coarse depths are stratified uniformly inside
+ * it.  Linear in depth only; the gaps inside a span are not skipped.  fp32, every operation rounded on
+ * its own, no FMA.  For ray r, K objects (1 <= K <= CN_MAX_SCENE_OBJECTS) each with its own rays
+ * ro_k, rd_k in its own frame (cn_object_rays: a rigid pose keeps the ray parameter) and its grid
+ * (bits_k, g_k, lo_k, inv_cell_k), near < far, P = n_probes:
+ *   probe depths  step = (far - near) / (float)(P - 1);  d_j = near + (float)j * step for j < P - 1,
+ *                 d_{P-1} = far exactly;
+ *   probe lookup  probe j is occupied iff for some k the point lookup above finds a set bit at
+ *                 p = rd_k[r] * d_j + ro_k[r] (product and sum each rounded, as cn_occupancy_cull forms
+ *                 it); a NaN or out-of-cube point is unoccupied;
+ *   span indices  first / last = the lowest / highest occupied j.  None: the ray is a MISS, first =
+ *                 last = -1, a = 0, b = P - 1 (it keeps the whole range; the grid culls its samples as
+ *                 before).  Otherwise a = max(first - 1, 0), b = min(last + 1, P - 1); b > a always;
+ *   depths        t_lo = d_a, t_hi = d_b, w = (t_hi - t_lo) / (float)(nc - 1);
+ *                 z_i = min(t_lo + ((float)i + tau_i) * w, t_hi) for i <= nc - 2, tau_i = t_rand[r][i]
+ *                 (0 without t_rand);  z_{nc-1} = t_hi exactly, always.
+ * Every rounding is monotone, so a row is non-decreasing (ties can occur: tau may be the largest float
+ * below 1).  volume_render gives the last sample the 1e10 interval; when last < P - 1, z_{nc-1} has the
+ * bits of an unoccupied probe, cn_occupancy_cull forms the same point from them, and the sample is culled
+ * for every object: the last real sample's interval ends at t_hi, not at infinity.  When last = P - 1
+ * the ray ends inside occupied space at far, as the plain sampler's does.
+ * The span is not strictly conservative: an occupied cell crossed only between two unoccupied probes
+ * outside [a, b] (a corner clip shorter than one probe step) is left out; a grid dilated by one cell
+ * (cn_occupancy_build's dilate = 1) covers that. */
+
+/* The rule above.  ro, rd: device (n_objects, n_rays, 3).  bits (device pointers), g, lo, inv_cell: HOST
+ * arrays of n_objects.  n_probes: a multiple of 64 in [64, 1024]; nc in [2, 512].  t_rand: (n_rays, nc)
+ * -- cn_sample_uniform's shape, columns 0 .. nc - 2 are read -- or NULL.  Outputs, every element
+ * written: z_out (n_rays, nc); span (n_rays, 2) = (t_lo, t_hi); probe_range (n_rays, 2) int32 =
+ * (first, last).  One launch on `stream`: no workspace, no atomics, no synchronisation.
+ * CN_EINVAL before any launch: a required pointer or an entry of bits NULL; n_objects outside
+ * 1..CN_MAX_SCENE_OBJECTS; n_rays <= 0; n_probes or nc outside the ranges above; a g[k] that
+ * cn_occupancy_build refuses; near or far not finite, near < 0 or far <= near; an inv_cell[k] or lo[k]
+ * that is not finite. */
+int cn_sample_span(const float* ro, const float* rd, int64_t n_rays, const uint32_t* const* bits,
+                   const int64_t* g, const float* lo, const float* inv_cell, int n_objects, float near,
+                   float far, int64_t n_probes, int64_t nc, const float* t_rand, float* z_out, float* span,
+                   int32_t* probe_range, cn_stream_t stream);
+
 /* --- Weight-bounded colour culling (inference) --------------------------
  * A ray's volume-render weights depend on its densities alone, so a pass that has the densities of
  * every sample (cn_density_field) and their weights (cn_volume_render) can leave out the colour
