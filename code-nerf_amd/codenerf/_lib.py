@@ -120,6 +120,11 @@ SIGNATURES = {
                             _p, _p, _p, _p, _p]),
     "cn_weight_cull": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _f, ctypes.c_double, _p, _p, _p, _p, _p, _p, _p]),
     "cn_scatter_rgb": (_i, [_p, _p, _i64, _p, _i64, _p]),
+    "cn_radiance_field_counted": (_i, [_p, _i, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _p, _fp, _fp, _p, _p]),
+    "cn_radiance_field_fold_counted": (_i, [_p, _i, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _p, _fp, _fp, _p,
+                                            _p]),
+    "cn_density_field_counted": (_i, [_p, _i, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _p, _fp, _p, _p, _p]),
+    "cn_scatter_rgb_counted": (_i, [_p, _p, _p, _i64, _p, _i64, _p]),
     "cn_volume_render_compose": (_i, [ctypes.POINTER(_p), _i, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p]),
     "cn_object_rays": (_i, [_p, _p, _i64, _fp, _i, _p, _p, _p]),
     "cn_volume_render_compose_backward": (_i, [ctypes.POINTER(_p), _i, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p,

@@ -172,13 +172,15 @@ def density_code_bias(m, cs: torch.Tensor) -> torch.Tensor:
 
 
 def _field_op(m: CodeNeRFModel, cs, ct, rd, chunk_rows, fx, fd, pts=None, ro=None, z=None, code_index=None,
-              pair=None):
+              pair=None, count=None):
     """The fused radiance field (encode + MLP) of ``m`` on distinct code rows cs / ct (``pair``: the render's
-    autograd.FieldPair, or None)."""
+    autograd.FieldPair, or None; ``count``: ops.radiance_field's device row count, inference only)."""
     needs_grad = torch.is_grad_enabled() and (
         any(t is not None and t.requires_grad for t in (rd, cs, ct, pts, ro)) or
         any(p.requires_grad for p in m.param_list()))
     if needs_grad:
+        if count is not None:
+            raise ValueError("a counted field call (count=) is an inference call: it has no backward")
         from ..autograd import radiance_field_autograd
         return radiance_field_autograd(m, rd, cs, ct, chunk_rows, fx, fd, pts=pts, ro=ro, z=z,
                                        code_index=code_index, pair=pair)
@@ -186,7 +188,7 @@ def _field_op(m: CodeNeRFModel, cs, ct, rd, chunk_rows, fx, fd, pts=None, ro=Non
     n_samples = pts.shape[1] if pts is not None else z.shape[1]
     packed, fmt, fold = inference_pack(m, cb)
     return ops.radiance_field(packed, cb, rd, n_samples, chunk_rows, fx, fd, pts=pts, ro=ro, z=z,
-                              code_index=code_index, precision=fmt, fold_bias=fold)
+                              code_index=code_index, precision=fmt, fold_bias=fold, count=count)
 
 
 def _dedupe_codes(z_s: torch.Tensor, z_t: torch.Tensor):

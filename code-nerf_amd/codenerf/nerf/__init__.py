@@ -413,10 +413,21 @@ class OccupancyGrid:
         return set_bits / float(self.resolution ** 3)
 
 
-def _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy: OccupancyGrid, density_only: bool):
+def _check_sync_free(*models):
+    """``sync_free=True`` runs the counted field entries, which exist for the fp32 16x16x4 kernels alone."""
+    for m in models:
+        if m is not None and _unwrap(m).kernel_format() != "f32_w16":
+            raise ValueError(f"sync_free=True needs models of precision 'f32' (the counted field kernels are fp32); "
+                             f"got precision {_unwrap(m).precision!r}")
+
+
+def _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy: OccupancyGrid, density_only: bool,
+                  sync_free: bool = False):
     """A render field call under an occupancy grid: cull -> ``model``'s inference field in points mode
     over the M' kept samples (the density kernel when ``density_only``) -> expand to raw (R, S, 4).
-    Kept samples get the bits of the unculled call; culled ones the zero-density row."""
+    Kept samples get the bits of the unculled call; culled ones the zero-density row.
+    ``sync_free``: M' stays on the device -- the field runs its counted entry over the compact buffers at
+    capacity and computes the first M' rows, the same bits."""
     from ..models.model import _field_op, density_code_bias
     fx, fd = _check_embedders(embedders)
     cs, ct, code_index = _codes(z_s, z_t)
@@ -425,9 +436,17 @@ def _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy: 
         many = cs.shape[0] > 1
         count, _, pts, vdir, code_out, state = ops.occupancy_cull(
             ro.detach(), rd.detach(), z, chunk_rows, occupancy.bits, occupancy.resolution, occupancy.bound,
-            code_index=code_index, want_code=many)
+            code_index=code_index, want_code=many, sync=not sync_free)
         raw = None
-        if count:
+        if sync_free:
+            index, cap = (code_out if many else None), pts.shape[0]
+            if cap and density_only:
+                raw = ops.density_field(m.packed(), density_code_bias(m, cs), fx, pts=pts, code_index=index,
+                                        want_sigma=False, want_raw=True, count=count)
+            elif cap:
+                raw = _field_op(m, cs.detach(), ct.detach(), vdir, cap, fx, fd, pts=pts.view(cap, 1, 3),
+                                code_index=index, count=count)
+        elif count:
             index = code_out if many else None
             if density_only:
                 raw = ops.density_field(m.packed(), density_code_bias(m, cs), fx, pts=pts, code_index=index,
@@ -439,11 +458,12 @@ def _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy: 
 
 
 def _weight_culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, tolerance: float,
-                         occupancy: Optional[OccupancyGrid]):
+                         occupancy: Optional[OccupancyGrid], sync_free: bool = False):
     """The fine field call under ``rgb_tolerance``: densities of every sample (the density kernel, under
     the grid when there is one) -> the render's own weights -> cull by weight -> ``model``'s inference
     field in points mode over the kept samples, its colours scattered into the density rows -> raw
-    (R, S, 4).  Every row keeps its sigma_raw; a culled one has raw colours [0, 0, 0]."""
+    (R, S, 4).  Every row keeps its sigma_raw; a culled one has raw colours [0, 0, 0].
+    ``sync_free``: as _culled_field's -- the kept count stays on the device for the field and the scatter."""
     from ..models.model import _field_op
     fx, fd = _check_embedders(embedders)
     cs, ct, code_index = _codes(z_s, z_t)
@@ -453,13 +473,21 @@ def _weight_culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, tole
         if occupancy is None:
             raw = _density_field_raw(model, embedders, rd, z_s, z_t, chunk_rows, ro=ro, z=z)
         else:       # the grid's empty rows have weight exactly 0: they fall out by w > 0
-            raw = _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy, density_only=True)
+            raw = _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy, density_only=True,
+                                sync_free=sync_free)
         weights = ops.volume_render(raw, z, rd)[3]
         eps_weight, eps_tail = ops.weight_cull_thresholds(tolerance, z.shape[1])
         many = cs.shape[0] > 1
         count, sample_index, pts, vdir, code_out, _ = ops.weight_cull(
-            weights, ro, rd, z, chunk_rows, eps_weight, eps_tail, code_index=code_index, want_code=many)
-        if count:
+            weights, ro, rd, z, chunk_rows, eps_weight, eps_tail, code_index=code_index, want_code=many,
+            sync=not sync_free)
+        if sync_free:
+            cap = pts.shape[0]
+            if cap:
+                kept = _field_op(m, cs.detach(), ct.detach(), vdir, cap, fx, fd, pts=pts.view(cap, 1, 3),
+                                 code_index=code_out if many else None, count=count)
+                ops.scatter_rgb(kept, sample_index, raw, count=count)
+        elif count:
             kept = _field_op(m, cs.detach(), ct.detach(), vdir, count, fx, fd, pts=pts.view(count, 1, 3),
                              code_index=code_out if many else None)
             ops.scatter_rgb(kept, sample_index, raw)
@@ -484,7 +512,7 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
                 coarse_only: bool = False, events: Optional[dict] = None,
                 coarse_rgb: bool = True, occupancy: Optional[OccupancyGrid] = None,
                 rgb_tolerance: Optional[float] = None, normals: bool = False,
-                span_probes: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                span_probes: Optional[int] = None, sync_free: bool = False) -> Dict[str, torch.Tensor]:
     """predict_radiance_and_render over a whole ray list, chunk semantics kept via ``chunk_rows``.
 
     Returns rgb/depth/acc for the coarse pass (+ weights) and, unless
@@ -500,7 +528,7 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     culls its samples against the grid, runs the field over the kept ones alone and expands the result;
     a culled sample has exactly zero density (not the reference's softplus tail), a kept one the
     unculled call's bits.  The kept count is read back on the host once per field call, so this
-    render is not graph-capturable.
+    render is not graph-capturable unless ``sync_free=True``.
     ``rgb_tolerance`` (inference only; needs a fine pass): a bound on the weight the fine pass may leave
     uncoloured per ray.  The fine pass then runs the density kernel over every fine sample, forms the
     render's weights from those densities, and runs the colour layers only for the samples kept by
@@ -509,7 +537,8 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     "acc_fine", "disp_fine" and the coarse entries are bitwise the plain call's; each channel of
     "rgb_fine" is within 0.501 x (the ray's culled weight, <= tol) of it, plus fp32 summation rounding.
     0.0 culls only samples of weight 0 or NaN.  Composes with ``occupancy``.  The kept count is read
-    back on the host once (ops.weight_cull), so this render is not graph-capturable either.
+    back on the host once (ops.weight_cull), so this render is not graph-capturable either unless
+    ``sync_free=True``.
     ``normals`` (inference only; needs a fine pass): adds "normal_fine" (R, 3) = sum_s w_s n_s, w the fine
     pass's compositing weights and n_s the unit normals (``normals``' rule) of the fine model's density at
     the fine samples, from one ops.density_gradient launch over (ro, rd, z_fine).  Not normalised: its
@@ -524,7 +553,16 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     depths is the same code path.  Adds "ray_span" (R, 2), the rays' (t_lo, t_hi), and "ray_hit" (R,) bool.
     The span is not strictly conservative (a corner clipped between two probes), which a grid dilated by one
     cell -- OccupancyGrid.from_density's default -- covers.
+    ``sync_free`` (models of precision "f32" only: ValueError otherwise): the culled field calls leave their kept
+    counts on the device.  Each runs the counted form of its kernel (include/codenerf.h) over the compact
+    buffers at capacity, sized for every sample and computing the kept rows alone, so nothing is read back
+    and the render can be captured in a graph and replayed on new inputs.  Every entry is bitwise the
+    ``sync_free=False`` result; composes with ``occupancy``, ``rgb_tolerance``, ``coarse_rgb=False``,
+    ``normals`` and ``span_probes``; without ``occupancy`` and ``rgb_tolerance`` nothing is culled and it
+    changes nothing.
     """
+    if sync_free:
+        _check_sync_free(coarse_model, None if coarse_only else fine_model)
     if span_probes is not None:
         if occupancy is None:
             raise ValueError("span_probes places the coarse samples by the occupancy grid: pass occupancy=")
@@ -580,14 +618,16 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
     if occupancy is not None:
         def culled(density_only):
             def field(model, embedders, rd, z_s, z_t, chunk_rows, ro=None, z=None, pair=None):
-                return _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy, density_only)
+                return _culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, occupancy, density_only,
+                                     sync_free)
             return field
         coarse_field, fine_field = culled(not coarse_rgb), culled(False)
     else:
         coarse_field, fine_field = (_field if coarse_rgb else _density_field_raw), _field
     if rgb_tolerance is not None:
         def fine_field(model, embedders, rd, z_s, z_t, chunk_rows, ro=None, z=None, pair=None):
-            return _weight_culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, rgb_tolerance, occupancy)
+            return _weight_culled_field(model, embedders, rd, z_s, z_t, chunk_rows, ro, z, rgb_tolerance, occupancy,
+                                        sync_free)
     if fine_model is not None and not coarse_only and coarse_rgb and occupancy is None and rgb_tolerance is None:
         # the two differentiable fields' pre-field launches (code terms, packs, zeroed accumulators) as
         # one launch; each field takes its part (no launch when either runs without gradients)
@@ -664,7 +704,7 @@ class SceneObject:
 def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: PointSampler, embedders, coarse_model,
                  fine_model=None, *, coarse_only: bool = False, coarse_rgb: bool = True,
                  t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
-                 span_probes: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                 span_probes: Optional[int] = None, sync_free: bool = False) -> Dict[str, torch.Tensor]:
     """Several posed objects (1..8 SceneObjects) in one image: render_rays' hierarchical render of the world
     rays ``ro`` / ``rd`` (R, 3), with the objects composed per sample.  A rigid pose keeps the ray
     parameter, so one set of depths along the world ray serves every object: the coarse depths
@@ -681,7 +721,9 @@ def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: Poi
     (each object's grid probed along its own object-frame ray), so the shared coarse depths cover every object the
     ray meets; adds "ray_span" and "ray_hit".
     Inference only.  Each object's kept count is read back once per field call -- 2 K host
-    synchronisations per render (K with ``coarse_only``) -- so this render is not graph-capturable."""
+    synchronisations per render (K with ``coarse_only``) -- so this render is not graph-capturable unless
+    ``sync_free=True`` (render_rays' argument: the counted field calls, the same bits, models of precision
+    "f32" only)."""
     objects = list(objects)
     if not 1 <= len(objects) <= 8 or not all(isinstance(o, SceneObject) for o in objects):
         raise ValueError(f"a scene holds 1..8 SceneObjects, got {len(objects)} entries")
@@ -697,6 +739,8 @@ def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: Poi
                          "backward (render under torch.no_grad())")
     if span_probes is not None:
         point_sampler.check_span_probes(span_probes)
+    if sync_free:
+        _check_sync_free(*(coarse_models + ([] if coarse_only else fine_models)))
     n = ro.shape[0]
     ps = point_sampler
     with torch.no_grad():
@@ -711,7 +755,8 @@ def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: Poi
                                                         span_probes)
 
         def fields(models, z, density_only):
-            return [_culled_field(m, embedders, rd_k[k], o.z_s, o.z_t, n, ro_k[k], z, o.occupancy, density_only)
+            return [_culled_field(m, embedders, rd_k[k], o.z_s, o.z_t, n, ro_k[k], z, o.occupancy, density_only,
+                                  sync_free)
                     for k, (o, m) in enumerate(zip(objects, models))]
 
         rgb_c, disp_c, acc_c, w_c, depth_c, obj_c = ops.volume_render_compose(fields(coarse_models, z_c, not coarse_rgb),
@@ -764,7 +809,8 @@ def render_scene_autograd(ro: torch.Tensor, rd: torch.Tensor, objects, point_sam
     can be fitted to an image or to per-instance masks ("acc_objects_*").  ``poses``: an optional (K, 12) float32
     device tensor that overrides the objects' host poses, each row the object-to-world rotation row-major, then
     the translation (``rigid_pose`` builds one from 6 numbers); it is read to the host once per render, one host
-    synchronisation more than render_scene's 2 K.
+    synchronisation more than render_scene's 2 K (there is no ``sync_free`` here: the backward sizes its buffers
+    by the kept counts).
     The path per object and pass: autograd.CullRows -> the fused fp32 field in points mode over the kept rows
     (frozen weights: its deterministic fused backward) -> autograd.ExpandRows; then autograd.VolumeRenderCompose.
     Every backward kernel reduces in a fixed order, so two runs give the same gradients.  The kept sets, the fine
@@ -834,7 +880,7 @@ def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, sam
                           key: str = "rgb_fine", coarse_only: bool = False,
                           coarse_rgb: bool = True, occupancy: Optional[OccupancyGrid] = None,
                           rgb_tolerance: Optional[float] = None,
-                          span_probes: Optional[int] = None) -> Optional[torch.Tensor]:
+                          span_probes: Optional[int] = None, sync_free: bool = False) -> Optional[torch.Tensor]:
     """nerf/__init__.py:137-226: shard the image's rays over ranks, render, gather on rank 0.
 
     The split is the reference's (Q5: truncating, the last rank takes the
@@ -846,6 +892,7 @@ def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, sam
     be "rgb_coarse".  ``occupancy``: an OccupancyGrid of the object, for render_rays' sample culling.
     ``rgb_tolerance``: render_rays' bound for the fine pass's weight-based colour culling.
     ``span_probes``: render_rays' probe count for per-ray coarse depth spans (needs ``occupancy``).
+    ``sync_free``: render_rays' flag -- the culled field calls read no kept count back.
     """
     if not coarse_rgb and key == "rgb_coarse":
         raise ValueError('coarse_rgb=False renders no coarse colours: key="rgb_coarse" needs coarse_rgb=True')
@@ -870,7 +917,7 @@ def parallel_image_render(cfg, pose: torch.Tensor, object_embedding, models, sam
         out = render_rays(ro[sl].to(device), rd[sl].to(device), z_s, z_t, point_sampler, embedders,
                           models["nerf_coarse"], models.get("nerf_fine"), cfg.nerf.validation.chunksize,
                           coarse_only=coarse_only, coarse_rgb=coarse_rgb, occupancy=occupancy,
-                          rgb_tolerance=rgb_tolerance, span_probes=span_probes)
+                          rgb_tolerance=rgb_tolerance, span_probes=span_probes, sync_free=sync_free)
         rgb = out[key]
         if not is_distributed:
             return rgb

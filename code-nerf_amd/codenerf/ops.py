@@ -112,6 +112,17 @@ def _point_inputs(freqs_xyz: Sequence[float], pts: Optional[Tensor], ro: Optiona
     return pts, ro, rd, z, x, _code_rows(code_index, n_codes, n), lead, n, s, _freqs(freqs_xyz, 10, "freqs_xyz")
 
 
+def _count_arg(count: Tensor, op: str, supported: bool, form: str) -> Tensor:
+    """The checked ``count`` of a counted call (include/codenerf.h): a (1,) int64 device tensor, which the
+    kernel reads when it runs; ``supported``: the call is in the form the counted entries take."""
+    if not supported:
+        raise ValueError(f"{op}: count= (a device row count) takes {form}")
+    count = _cuda(count, "count", torch.int64)
+    if count.numel() != 1:
+        raise ValueError(f"{op}: count must hold one int64, got shape {tuple(count.shape)}")
+    return count
+
+
 # ------------------------------------------------------------------ rays
 
 
@@ -610,8 +621,14 @@ def radiance_field(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int, chunk
                    freqs_xyz: Sequence[float], freqs_dir: Sequence[float], pts: Optional[Tensor] = None,
                    ro: Optional[Tensor] = None, z: Optional[Tensor] = None,
                    code_index: Optional[Tensor] = None, precision: str = "f32",
-                   fold_bias: Optional[Tensor] = None, view_rows: Optional[bool] = None) -> Tensor:
+                   fold_bias: Optional[Tensor] = None, view_rows: Optional[bool] = None,
+                   count: Optional[Tensor] = None) -> Tensor:
     """forward_pass (nerf/__init__.py:94-134) fused with the MLP -> raw (R, S, 4).
+    ``count`` (a (1,) int64 device tensor, e.g. occupancy_cull(sync=False)'s): the counted entries
+    (cn_radiance_field_counted / _fold_counted) -- R is the capacity, only the first min(max(count, 0), R)
+    rows are computed and written (the rest of ``raw`` stays uninitialised) and nothing is read back.
+    Points form with n_samples = 1, precision "f32_w16" or "f32_w16_fold", one code row or ``code_index``,
+    no view-rows table: ValueError otherwise.
     precision "f32_w16_fold": ``packed`` that format's pack and ``fold_bias`` = ops.fold_bias(params, cb).
     ``view_rows`` (that precision only): read layer_dir1's view-direction term from a per-ray table built
     here (ops.view_rows) instead of computing it per sample -- the same bits.  None: where it pays, i.e.
@@ -625,6 +642,20 @@ def radiance_field(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int, chunk
                                                         n_codes)
     raw = torch.empty(n, n_samples, 4, device=rd.device, dtype=torch.float32)
     one_code = n_codes == 1 and code_index is None
+    if count is not None:
+        count = _count_arg(count, "radiance_field", pts is not None and n_samples == 1 and not view_rows and
+                           precision in ("f32_w16", "f32_w16_fold") and (one_code or code_index is not None),
+                           "the points form with n_samples=1, precision 'f32_w16' or 'f32_w16_fold', one code row "
+                           "or code_index, and no view_rows table")
+        if n and fold is not None:
+            check(lib.cn_radiance_field_fold_counted(ptr(packed), _fmt(precision), ptr(cb), ptr(fold), ptr(code_index),
+                                                     n_codes, ptr(pts), None, ptr(rd), None, n, 1, ptr(count), fx, fd,
+                                                     ptr(raw), stream_of(rd)), "cn_radiance_field_fold_counted")
+        elif n:
+            check(lib.cn_radiance_field_counted(ptr(packed), _fmt(precision), ptr(cb), ptr(code_index), n_codes,
+                                                ptr(pts), None, ptr(rd), None, n, 1, ptr(count), fx, fd, ptr(raw),
+                                                stream_of(rd)), "cn_radiance_field_counted")
+        return raw
     if view_rows is None:
         view_rows = fold is not None and pts is None and one_code and n_samples >= VIEW_ROWS_MIN_SAMPLES
     elif view_rows:
@@ -650,9 +681,12 @@ def radiance_field(packed: Tensor, cb: Tensor, rd: Tensor, n_samples: int, chunk
 def density_field(packed: Tensor, cb: Tensor, freqs_xyz: Sequence[float], *, pts: Optional[Tensor] = None,
                   ro: Optional[Tensor] = None, rd: Optional[Tensor] = None, z: Optional[Tensor] = None,
                   x: Optional[Tensor] = None, code_index: Optional[Tensor] = None, want_sigma: bool = True,
-                  want_raw: bool = False):
+                  want_raw: bool = False, count: Optional[Tensor] = None):
     """sigma_raw of CodeNeRFModel.forward alone (model.py:174-186; cn_density_field): the fp32 field
     kernel's first 10 weight chunks, bitwise the sigma_raw radiance_field gives for the same points.
+    ``count`` (a (1,) int64 device tensor): cn_density_field_counted, as radiance_field's -- ``pts`` (M, 3)
+    at capacity, one code row or ``code_index``, the first min(max(count, 0), M) rows written; ValueError
+    for the ray form, encoded rows or (R, S, 3) points.
 
     Exactly one input: ``pts`` (R, S, 3) or (M, 3) [R = M, S = 1]; ``ro``, ``rd`` (R, 3) with ``z`` (R, S);
     ``x`` (M, 63) or (M, 90) encoded rows [R = M, S = 1].  ``packed``: the "f32_w16" pack; ``cb`` one code
@@ -666,7 +700,15 @@ def density_field(packed: Tensor, cb: Tensor, freqs_xyz: Sequence[float], *, pts
     dev = (pts if pts is not None else x if x is not None else z).device
     sigma = torch.empty(lead, device=dev, dtype=torch.float32) if want_sigma else None
     raw = torch.empty(lead + (4,), device=dev, dtype=torch.float32) if want_raw else None
-    if n * s:      # no samples: empty outputs without a launch (the C ABI refuses sizes of 0)
+    if count is not None:
+        count = _count_arg(count, "density_field", pts is not None and pts.dim() == 2 and
+                           (n_codes == 1 or code_index is not None),
+                           "pts (M, 3) with one code row or code_index")
+        if n:
+            check(lib.cn_density_field_counted(ptr(packed), _lib.CN_FMT_F32_W16, ptr(cb), ptr(code_index), n_codes,
+                                               ptr(pts), None, None, None, n, 1, ptr(count), fx, ptr(sigma), ptr(raw),
+                                               stream_of(cb)), "cn_density_field_counted")
+    elif n * s:    # no samples: empty outputs without a launch (the C ABI refuses sizes of 0)
         check(lib.cn_density_field(ptr(packed), _lib.CN_FMT_F32_W16, ptr(cb), ptr(code_index), n_codes, ptr(pts),
                                    ptr(ro), ptr(rd), ptr(z), ptr(x), 0 if x is None else x.shape[1], n, s, fx,
                                    ptr(sigma), ptr(raw), stream_of(cb)), "cn_density_field")
@@ -723,7 +765,7 @@ def occupancy_build(nodes: Tensor, threshold: float, dilate: int = 1) -> Tensor:
 
 
 def occupancy_cull(ro: Tensor, rd: Tensor, z: Tensor, chunk_rows: int, bits: Tensor, resolution: int, bound: float,
-                   code_index: Optional[Tensor] = None, want_code: bool = True):
+                   code_index: Optional[Tensor] = None, want_code: bool = True, sync: bool = True):
     """Test every ray sample against an occupancy grid and compact the occupied ones
     (cn_occupancy_cull) -> (count, sample_index (M',) int32, pts (M', 3), vdir (M', 3), code_out (M',)
     int64 or None, state), M' = ``count`` samples in ascending sample order.  ``vdir`` holds the
@@ -733,7 +775,11 @@ def occupancy_cull(ro: Tensor, rd: Tensor, z: Tensor, chunk_rows: int, bits: Ten
 
     This is the one place that reads ``count`` back (``.item()``): a HOST SYNCHRONISATION, since the
     field launch over the compact rows is sized by it.  A culled render is therefore not
-    graph-capturable, although the C ABI entries themselves are stream-ordered and are."""
+    graph-capturable, although the C ABI entries themselves are stream-ordered and are -- unless
+    ``sync=False``: nothing is read back, ``count`` is the (1,) int64 device tensor, the compact outputs
+    come at full capacity (R S rows, the first ``count`` written) and go with ``count=`` to
+    radiance_field / density_field / scatter_rgb; ``state`` is one occupancy_expand accepts for a
+    compact result of that capacity."""
     lib = _lib_ready()
     ro, rd, z = _cuda(ro, "ro"), _cuda(rd, "rd"), _cuda(z, "z_vals")
     bits = _cuda(bits, "bits", torch.int32)
@@ -753,7 +799,8 @@ def occupancy_cull(ro: Tensor, rd: Tensor, z: Tensor, chunk_rows: int, bits: Ten
     vdir = torch.empty(m, 3, device=dev, dtype=torch.float32)
     code_out = torch.empty(m, device=dev, dtype=torch.int64) if want_code else None
     if m == 0:
-        return 0, sample_index, pts, vdir, code_out, (None, n, s, 0)
+        return (0 if sync else torch.zeros(1, device=dev, dtype=torch.int64)), sample_index, pts, vdir, code_out, \
+            (None, n, s, 0)
     ws_bytes = lib.cn_occupancy_cull_workspace_bytes(n, s)
     if ws_bytes < 0:
         raise ValueError(f"occupancy_cull: {n} rays x {s} samples is outside 1..512 samples / 2^31 - 1 rows")
@@ -763,6 +810,8 @@ def occupancy_cull(ro: Tensor, rd: Tensor, z: Tensor, chunk_rows: int, bits: Ten
     check(lib.cn_occupancy_cull(ptr(ro), ptr(rd), ptr(z), n, s, int(chunk_rows), ptr(code_index), ptr(bits), g, lo,
                                 inv_cell, ptr(workspace), ptr(count), ptr(sample_index), ptr(pts), ptr(vdir),
                                 ptr(code_out), stream_of(z)), "cn_occupancy_cull")
+    if not sync:
+        return count, sample_index, pts, vdir, code_out, (workspace, n, s, m)
     k = int(count.item())       # host synchronisation (see the docstring)
     return (k, sample_index[:k], pts[:k], vdir[:k], None if code_out is None else code_out[:k],
             (workspace, n, s, k))
@@ -909,7 +958,7 @@ def weight_cull_thresholds(tolerance: float, n_samples: int) -> Tuple[float, flo
 
 
 def weight_cull(weights: Tensor, ro: Tensor, rd: Tensor, z: Tensor, chunk_rows: int, eps_weight: float,
-                eps_tail: float, code_index: Optional[Tensor] = None, want_code: bool = True):
+                eps_tail: float, code_index: Optional[Tensor] = None, want_code: bool = True, sync: bool = True):
     """Compact the samples whose volume-render weight can matter (cn_weight_cull): sample i of a ray is
     kept iff w_i > 0, w_i >= eps_weight (fp32) and the double sum of w_i.. >= eps_tail; NaN fails.
     ``weights`` (R, S) as volume_render returns them -> occupancy_cull's tuple (count, sample_index,
@@ -917,7 +966,8 @@ def weight_cull(weights: Tensor, ro: Tensor, rd: Tensor, z: Tensor, chunk_rows: 
     occupancy_expand.
 
     Like occupancy_cull, this reads ``count`` back once (``.item()``): a HOST SYNCHRONISATION, since
-    the field launch over the kept rows is sized by it."""
+    the field launch over the kept rows is sized by it -- unless ``sync=False``, which returns the device
+    ``count`` and full-capacity outputs as occupancy_cull's does."""
     lib = _lib_ready()
     weights = _cuda(weights, "weights")
     ro, rd, z = _cuda(ro, "ro"), _cuda(rd, "rd"), _cuda(z, "z_vals")
@@ -938,7 +988,8 @@ def weight_cull(weights: Tensor, ro: Tensor, rd: Tensor, z: Tensor, chunk_rows: 
     vdir = torch.empty(m, 3, device=dev, dtype=torch.float32)
     code_out = torch.empty(m, device=dev, dtype=torch.int64) if want_code else None
     if m == 0:
-        return 0, sample_index, pts, vdir, code_out, (None, n, s, 0)
+        return (0 if sync else torch.zeros(1, device=dev, dtype=torch.int64)), sample_index, pts, vdir, code_out, \
+            (None, n, s, 0)
     ws_bytes = lib.cn_occupancy_cull_workspace_bytes(n, s)
     if ws_bytes < 0:
         raise ValueError(f"weight_cull: {n} rays x {s} samples is outside 1..512 samples / 2^31 - 1 rows")
@@ -947,15 +998,19 @@ def weight_cull(weights: Tensor, ro: Tensor, rd: Tensor, z: Tensor, chunk_rows: 
     check(lib.cn_weight_cull(ptr(weights), ptr(ro), ptr(rd), ptr(z), n, s, int(chunk_rows), ptr(code_index),
                              eps_weight, eps_tail, ptr(workspace), ptr(count), ptr(sample_index), ptr(pts), ptr(vdir),
                              ptr(code_out), stream_of(z)), "cn_weight_cull")
+    if not sync:
+        return count, sample_index, pts, vdir, code_out, (workspace, n, s, m)
     k = int(count.item())       # host synchronisation (see the docstring)
     return (k, sample_index[:k], pts[:k], vdir[:k], None if code_out is None else code_out[:k],
             (workspace, n, s, k))
 
 
-def scatter_rgb(raw_compact: Tensor, sample_index: Tensor, raw: Tensor) -> Tensor:
+def scatter_rgb(raw_compact: Tensor, sample_index: Tensor, raw: Tensor, count: Optional[Tensor] = None) -> Tensor:
     """The colours of the compact field rows (M', 4) into ``raw`` (.., 4) IN PLACE (cn_scatter_rgb):
     components 0..2 of row ``sample_index[j]`` from compact row j; component 3 (sigma_raw) and every
-    other row stay as they are -> ``raw``.  Nothing is launched when no row was kept."""
+    other row stay as they are -> ``raw``.  Nothing is launched when no row was kept.
+    ``count`` (a (1,) int64 device tensor): cn_scatter_rgb_counted -- ``raw_compact`` and ``sample_index``
+    at capacity, the first min(max(count, 0), capacity) rows scattered, the others' indices not read."""
     lib = _lib_ready()
     sample_index = _cuda(sample_index, "sample_index", torch.int32)
     k = sample_index.shape[0]
@@ -967,6 +1022,11 @@ def scatter_rgb(raw_compact: Tensor, sample_index: Tensor, raw: Tensor) -> Tenso
         return raw
     raw_compact = _aligned16(_cuda(raw_compact, "raw_compact").reshape(-1, 4))
     assert raw_compact.shape[0] == k, f"raw_compact must hold the {k} kept rows"
+    if count is not None:
+        count = _count_arg(count, "scatter_rgb", True, "")
+        check(lib.cn_scatter_rgb_counted(ptr(raw_compact), ptr(sample_index), ptr(count), k, ptr(raw), n_slots,
+                                         stream_of(raw)), "cn_scatter_rgb_counted")
+        return raw
     check(lib.cn_scatter_rgb(ptr(raw_compact), ptr(sample_index), k, ptr(raw), n_slots, stream_of(raw)),
           "cn_scatter_rgb")
     return raw

@@ -161,6 +161,36 @@ int radiance_field_any(const float* packed, int fmt, bool fold_entry, const floa
   return launch_field(fmt, geometry_mode(a), a, cn::as_stream(stream));
 }
 
+// What the counted entries add to their parents' rules (include/codenerf.h): the one format, the points
+// form with one sample per row, codes by one row or code_index, and the device row count.
+int counted_status(int fmt, int want_fmt, const float* pts, const float* ro, const float* z, int64_t n_rows_max,
+                   int64_t n_samples, const int64_t* code_index, int64_t n_codes, const int64_t* count) {
+  CN_CHECK_ARG(fmt == want_fmt);
+  CN_CHECK_ARG(pts && !ro && !z && n_samples == 1 && n_rows_max > 0);
+  CN_CHECK_ARG(code_index || n_codes == 1);
+  CN_CHECK_ARG(count && (reinterpret_cast<uintptr_t>(count) & 7) == 0);
+  return CN_OK;
+}
+
+// cn_radiance_field_counted / cn_radiance_field_fold_counted
+int radiance_field_counted_any(const float* packed, int fmt, bool fold_entry, const float* code_bias,
+                               const float* fold_bias, const int64_t* code_index, int64_t n_codes, const float* pts,
+                               const float* ro, const float* rd, const float* z, int64_t n_rows_max, int64_t n_samples,
+                               const int64_t* count, const float* freqs_xyz, const float* freqs_dir, float* raw,
+                               cn_stream_t stream) {
+  CN_TRY(counted_status(fmt, fold_entry ? CN_FMT_F32_W16_FOLD : CN_FMT_F32_W16, pts, ro, z, n_rows_max, n_samples,
+                        code_index, n_codes, count));
+  CN_CHECK_ARG(!fold_entry || fold_bias);
+  CN_CHECK_ARG(cn::aligned16(fold_bias));  // 16-B vector reads of a c_v1 row
+  // the capacity as n_rays = chunk_rows: with one sample per row the Q1 ray is the row itself
+  const FieldInputs in = {pts, nullptr, rd, nullptr, n_rows_max, 1, n_rows_max, code_index, n_codes, freqs_xyz,
+                          freqs_dir};
+  FieldArgs a;
+  CN_TRY(forward_args(in, packed, code_bias, raw, a));
+  a.fold_bias = fold_bias;
+  return launch_field_w16_counted(fold_entry, a, count, cn::as_stream(stream));
+}
+
 }  // namespace
 
 extern "C" int64_t cn_mlp_packed_floats(int fmt) {
@@ -256,6 +286,25 @@ extern "C" int cn_radiance_field_fold(const float* packed, int fmt, const float*
   return radiance_field_any(packed, fmt, true, code_bias, fold_bias, in, raw, stream);
 }
 
+extern "C" int cn_radiance_field_counted(const float* packed, int fmt, const float* code_bias,
+                                         const int64_t* code_index, int64_t n_codes, const float* pts,
+                                         const float* ro, const float* rd, const float* z, int64_t n_rows_max,
+                                         int64_t n_samples, const int64_t* count, const float* freqs_xyz,
+                                         const float* freqs_dir, float* raw, cn_stream_t stream) {
+  return radiance_field_counted_any(packed, fmt, false, code_bias, nullptr, code_index, n_codes, pts, ro, rd, z,
+                                    n_rows_max, n_samples, count, freqs_xyz, freqs_dir, raw, stream);
+}
+
+extern "C" int cn_radiance_field_fold_counted(const float* packed, int fmt, const float* code_bias,
+                                              const float* fold_bias, const int64_t* code_index, int64_t n_codes,
+                                              const float* pts, const float* ro, const float* rd, const float* z,
+                                              int64_t n_rows_max, int64_t n_samples, const int64_t* count,
+                                              const float* freqs_xyz, const float* freqs_dir, float* raw,
+                                              cn_stream_t stream) {
+  return radiance_field_counted_any(packed, fmt, true, code_bias, fold_bias, code_index, n_codes, pts, ro, rd, z,
+                                    n_rows_max, n_samples, count, freqs_xyz, freqs_dir, raw, stream);
+}
+
 extern "C" int64_t cn_view_rows_bytes(int64_t n_rays) {
   return (n_rays > 0 && n_rays <= INT64_MAX / (kHidden * 4)) ? n_rays * kHidden * 4 : -1;
 }
@@ -310,6 +359,25 @@ extern "C" int cn_density_field(const float* packed, int fmt, const float* code_
   d.sigma = sigma;
   d.x_stride = x_stride;
   return launch_density_w16(geometry_mode(d.f), d, cn::as_stream(stream));
+}
+
+extern "C" int cn_density_field_counted(const float* packed, int fmt, const float* code_bias,
+                                        const int64_t* code_index, int64_t n_codes, const float* pts, const float* ro,
+                                        const float* rd, const float* z, int64_t n_rows_max, int64_t n_samples,
+                                        const int64_t* count, const float* freqs_xyz, float* sigma, float* raw,
+                                        cn_stream_t stream) {
+  CN_TRY(counted_status(fmt, CN_FMT_F32_W16, pts, ro, z, n_rows_max, n_samples, code_index, n_codes, count));
+  CN_CHECK_ARG(!rd && packed && code_bias && (sigma || raw));
+  CN_CHECK_ARG(cn::aligned16(raw));  // float4 rows (include/codenerf.h)
+  const FieldInputs in = {pts, nullptr, nullptr, nullptr, n_rows_max, 1, 0, code_index, n_codes, freqs_xyz, nullptr,
+                          nullptr};
+  DensityArgs d = {};
+  CN_TRY(field_args(in, kDensityForm, 0, d.f));
+  d.f.packed = packed;
+  d.f.code_bias = code_bias;
+  d.f.raw = raw;
+  d.sigma = sigma;
+  return launch_density_w16_counted(d, count, cn::as_stream(stream));
 }
 
 extern "C" int cn_density_gradient(const float* packed, const float* packed_t, int fmt, int fmt_t,

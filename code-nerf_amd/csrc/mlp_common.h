@@ -324,6 +324,10 @@ int launch_field_w16_fold(int mode, FieldArgs& a, hipStream_t st);
 // row, geometry from points or rays)
 int launch_view_rows_w16(FieldArgs& a, float* rows, hipStream_t st);
 int launch_field_w16_fold_rows(int mode, FieldArgs& a, hipStream_t st);
+// the counted forms (cn_*_counted): points, one sample per row, a.m / d.f.m the capacity the launch is
+// sized by, the row count read from device memory by the kernel (fold: the folded forward)
+int launch_field_w16_counted(bool fold, FieldArgs& a, const int64_t* count, hipStream_t st);
+int launch_density_w16_counted(DensityArgs& d, const int64_t* count, hipStream_t st);
 int launch_pack_w16t(const Params& P, float* packed, hipStream_t st);
 // code_bias + the CN_FMT_F32_W16 / _T packs + a zeroed buffer (any of them null: skipped), for one or
 // two models on the same codes, in one launch

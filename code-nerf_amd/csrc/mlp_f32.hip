@@ -902,7 +902,12 @@ __device__ __forceinline__ void view_dir_enc(const float (&vd)[3], const float (
 // move to the accumulators once relu(h2) has left them; the rest are issued then, ahead of
 // sigma_partial, and waited for with vmcnt(0) after it (the ring's pieces in flight before them retire
 // first, so the next barrier's counted vmcnt still holds).
-template <int MODE, bool MASKS, bool SAVE = false, bool FOLD = false, bool ROWS = false>
+//
+// TAG changes nothing in the tile: it gives a second kernel over the same variant an instantiation of
+// its own (kTagCounted: the counted kernels).  A tile function shared by two kernels is inlined in
+// another order, and the kernel that had it to itself then compiles to other scalar code.
+constexpr int kTagCounted = 1;
+template <int MODE, bool MASKS, bool SAVE = false, bool FOLD = false, bool ROWS = false, int TAG = 0>
 __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4* lds, float* clds, float* crow_lds,
                                           int64_t tile, int& c, int64_t next = -1) {
   static_assert(!FOLD || (!MASKS && !SAVE), "the folded kernel has no feat plane and no fc_out input gradient");
@@ -1240,6 +1245,57 @@ __global__ __launch_bounds__(kThreads, 2) void field_w16_kernel(FieldArgs a) {
   __builtin_amdgcn_s_waitcnt(0x0F70);
 }
 
+// The row count of a counted launch (cn_*_counted, include/codenerf.h): count[0] clamped to 0..capacity.
+__device__ __forceinline__ int64_t counted_rows(const int64_t* count, int64_t capacity) {
+  const int64_t k = count[0];
+  return k < 0 ? 0 : (k < capacity ? k : capacity);
+}
+
+// field_w16_kernel<kFromPts, false, false, FOLD> launched for a.m = the capacity, with the row count in
+// device memory: a kernel of its own, so that field_w16_kernel's instantiations keep their code (its
+// prologue and tile loop are repeated here, without the table variant's parts).  The tiles run with
+// a.m = k, so the tile count, the partial tile's rows and the row clamps are the k-row launch's;
+// a.n_rays = a.chunk_rows stay the capacity (one sample per row: the Q1 ray is the row itself).  A
+// workgroup whose first tile is past k primes the ring, runs no tile and drains: the wait below covers
+// its three chunks.  k = 0 decodes no row at all.
+template <bool FOLD>
+__global__ __launch_bounds__(kThreads, 2) void field_w16_counted_kernel(FieldArgs cap,
+                                                                        const int64_t* __restrict__ count) {
+  __shared__ __attribute__((aligned(16))) float4 lds[kLdsQuads];  // one LDS object, as field_w16_kernel
+  // the tiles' arguments: a copy that lives in registers (load_consts indexes the frequency tables by
+  // lane, which would put a modified copy in scratch memory: it reads the kernel's own argument)
+  FieldArgs a = cap;
+  a.m = counted_rows(count, cap.m);
+  float* clds = reinterpret_cast<float*>(lds + kRing * kChunkQuads);
+  State s;
+  s.lane = threadIdx.x & 63;
+  s.g = s.lane >> 4;
+  s.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  constexpr int NG = FOLD ? kStreamFold : kStreamFull;
+  s.cbase = 0;
+  s.wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.packed), 0,
+                                             (FOLD ? kFoldPackedFloats : kPackedFloats) * 4, 0x00020000);
+  s.voff = static_cast<unsigned>(s.wave * 64 + s.lane) * 16u;
+  s.poff = static_cast<unsigned>(s.wave * 16 + (s.lane & 15)) * 1024u + 16u * s.g;
+  s.sig = 0.0f;
+  float* crow_lds = clds + kLdsConsts + s.wave * kCbStride;
+
+  load_consts(cap, clds, FOLD ? kFoldStreamFloats : kStreamFloats);
+  dma_chunk<NG>(s, lds, 0);
+  dma_chunk<NG>(s, lds, 1);
+  dma_chunk<NG>(s, lds, 2);
+  asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  read_a<0>(lds + s.lane, s.pre);
+
+  const int64_t n_tiles = (a.m + kTile - 1) / kTile;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    int c = 0;
+    field_tile<kFromPts, false, false, FOLD, false, kTagCounted>(s, a, lds, clds, crow_lds, tile, c);
+  }
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+}
+
 
 // ================================================================ per-ray view-direction rows
 // rows[ray] (256 floats, feature order) = what the folded kernel's accumulators hold after
@@ -1318,8 +1374,8 @@ __device__ __forceinline__ uint2v opaque_mask(uint2v w) {
 
 // The forward of sample row rc through chunks c .. c + 9 of stream NG; returns sigma_raw (every lane
 // group holds it).  x: the point (left as it is in kFromEncoded); MASKS: the ReLU mask words of h1 and h2
-// (relu_act) into m_h1, m_h2 -- the density-gradient kernel's backward reads both.
-template <int MODE, int NG = kStreamSigma, bool MASKS = false>
+// (relu_act) into m_h1, m_h2 -- the density-gradient kernel's backward reads both.  TAG: field_tile's.
+template <int MODE, int NG = kStreamSigma, bool MASKS = false, int TAG = 0>
 __device__ __forceinline__ float sigma_forward(State& s, const DensityArgs& d, float4* lds, float* clds,
                                               float* crow_lds, int64_t rc, int& c, float (&x)[3], uint2v& m_h1,
                                               uint2v& m_h2) {
@@ -1419,7 +1475,7 @@ __device__ __forceinline__ float sigma_forward(State& s, const DensityArgs& d, f
   return sg + bs;
 }
 
-template <int MODE>
+template <int MODE, int TAG = 0>
 __device__ __forceinline__ void sigma_tile(State& s, const DensityArgs& d, float4* lds, float* clds, float* crow_lds,
                                           int64_t tile, int& c) {
   const FieldArgs& a = d.f;
@@ -1429,7 +1485,7 @@ __device__ __forceinline__ void sigma_tile(State& s, const DensityArgs& d, float
   s.cbase = c;
   float x[3] = {0.0f, 0.0f, 0.0f};
   uint2v m_h1, m_h2;
-  const float sg = sigma_forward<MODE>(s, d, lds, clds, crow_lds, rc, c, x, m_h1, m_h2);
+  const float sg = sigma_forward<MODE, kStreamSigma, false, TAG>(s, d, lds, clds, crow_lds, rc, c, x, m_h1, m_h2);
   if (valid && s.g == 0) {
     if (d.sigma) d.sigma[row] = sg;
     if (a.raw) reinterpret_cast<float4*>(a.raw)[row] = make_float4(0.0f, 0.0f, 0.0f, sg);
@@ -1465,6 +1521,39 @@ __global__ __launch_bounds__(kThreads, 2) void density_w16_kernel(DensityArgs d)
     sigma_tile<MODE>(s, d, lds, clds, crow_lds, tile, c);
   // the last tile prefetched three chunks of a tile that does not exist: they must land before
   // the workgroup's LDS is released
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+}
+
+// density_w16_kernel<kFromPts> launched for the capacity with the row count in device memory
+// (cn_density_field_counted), a kernel of its own as field_w16_counted_kernel: the tiles run with
+// d.f.m = k, a workgroup without a tile primes the ring and drains.
+__global__ __launch_bounds__(kThreads, 2) void density_w16_counted_kernel(DensityArgs cap,
+                                                                          const int64_t* __restrict__ count) {
+  __shared__ __attribute__((aligned(16))) float4 lds[kSigLdsQuads];
+  DensityArgs d = cap;  // in registers; load_consts reads the kernel's own argument
+  d.f.m = counted_rows(count, cap.f.m);
+  float* clds = reinterpret_cast<float*>(lds + kRing * kChunkQuads);
+  State s;
+  s.lane = threadIdx.x & 63;
+  s.g = s.lane >> 4;
+  s.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  s.wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.f.packed), 0, kPackedFloats * 4, 0x00020000);
+  s.voff = static_cast<unsigned>(s.wave * 64 + s.lane) * 16u;
+  s.cbase = 0;
+  float* crow_lds = clds + kLdsConsts + s.wave * 256;
+
+  load_consts(cap.f, clds);
+  dma_chunk<kStreamSigma>(s, lds, 0);
+  dma_chunk<kStreamSigma>(s, lds, 1);
+  dma_chunk<kStreamSigma>(s, lds, 2);
+  asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  read_a<0>(lds + s.lane, s.pre);
+
+  const int64_t n_tiles = (d.f.m + kTile - 1) / kTile;
+  int c = 0;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
+    sigma_tile<kFromPts, kTagCounted>(s, d, lds, clds, crow_lds, tile, c);
   __builtin_amdgcn_s_waitcnt(0x0F70);
 }
 
@@ -2377,6 +2466,25 @@ int launch_density_w16(int mode, DensityArgs& d, hipStream_t st) {
     case kFromRayZ: hipLaunchKernelGGL((w16::density_w16_kernel<kFromRayZ>), dim3(grid), b, 0, st, d); break;
     default: hipLaunchKernelGGL((w16::density_w16_kernel<kFromEncoded>), dim3(grid), b, 0, st, d); break;
   }
+  return cn::launch_status();
+}
+
+// The counted launches (points form, a.m = the capacity): the grid of a launch over a.m rows -- the
+// kernel takes its rows from count[0] -- and one launch, as their parents'.
+int launch_field_w16_counted(bool fold, FieldArgs& a, const int64_t* count, hipStream_t st) {
+  if (!count || !a.pts || a.n_samples != 1 || a.masks || a.save || a.view_rows || (fold && !a.fold_bias))
+    return CN_EINVAL;
+  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(a.m, w16::kTile), cu_count_w16()));
+  const dim3 b(w16::kThreads);
+  if (fold) hipLaunchKernelGGL((w16::field_w16_counted_kernel<true>), dim3(grid), b, 0, st, a, count);
+  else hipLaunchKernelGGL((w16::field_w16_counted_kernel<false>), dim3(grid), b, 0, st, a, count);
+  return cn::launch_status();
+}
+
+int launch_density_w16_counted(DensityArgs& d, const int64_t* count, hipStream_t st) {
+  if (!count || !d.f.pts || d.f.n_samples != 1) return CN_EINVAL;
+  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(d.f.m, w16::kTile), cu_count_w16()));
+  hipLaunchKernelGGL(w16::density_w16_counted_kernel, dim3(grid), dim3(w16::kThreads), 0, st, d, count);
   return cn::launch_status();
 }
 

@@ -244,6 +244,22 @@ __global__ __launch_bounds__(256) void scatter_rgb_kernel(const float4* __restri
   *reinterpret_cast<float3*>(raw + 4 * static_cast<size_t>(k)) = make_float3(v.x, v.y, v.z);
 }
 
+// scatter_rgb_kernel with the row count in device memory (cn_scatter_rgb_counted): the launch covers
+// n_rows_max rows, the rows past min(max(count[0], 0), n_rows_max) read no index and store nothing.
+__global__ __launch_bounds__(256) void scatter_rgb_counted_kernel(const float4* __restrict__ raw_compact,
+                                                                  const int* __restrict__ sample_index,
+                                                                  const int64_t* __restrict__ count, int n_rows_max,
+                                                                  float* __restrict__ raw, int n_slots) {
+  const int64_t c = count[0];
+  const int n_rows = c < 0 ? 0 : (c < n_rows_max ? static_cast<int>(c) : n_rows_max);
+  const int j = static_cast<int>(blockIdx.x * 256u + threadIdx.x);
+  if (j >= n_rows) return;
+  const int k = sample_index[j];
+  if (static_cast<unsigned>(k) >= static_cast<unsigned>(n_slots)) return;   // never a store outside raw
+  const float4 v = raw_compact[j];
+  *reinterpret_cast<float3*>(raw + 4 * static_cast<size_t>(k)) = make_float3(v.x, v.y, v.z);
+}
+
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 // What the two cull entries share: their common argument rules ...
@@ -324,6 +340,16 @@ extern "C" int cn_scatter_rgb(const float* raw_compact, const int32_t* sample_in
   hipLaunchKernelGGL(scatter_rgb_kernel, dim3(static_cast<unsigned>(cn::ceil_div(n_rows, 256))), dim3(256), 0,
                      cn::as_stream(stream), reinterpret_cast<const float4*>(raw_compact), sample_index,
                      static_cast<int>(n_rows), raw, static_cast<int>(n_slots));
+  return cn::launch_status();
+}
+
+extern "C" int cn_scatter_rgb_counted(const float* raw_compact, const int32_t* sample_index, const int64_t* count,
+                                      int64_t n_rows_max, float* raw, int64_t n_slots, cn_stream_t stream) {
+  CN_CHECK_ARG(raw_compact && sample_index && raw && n_slots <= INT_MAX && n_rows_max >= 1 && n_rows_max <= n_slots);
+  CN_CHECK_ARG(count && aligned8(count) && cn::aligned16(raw_compact) && cn::aligned16(raw));
+  hipLaunchKernelGGL(scatter_rgb_counted_kernel, dim3(static_cast<unsigned>(cn::ceil_div(n_rows_max, 256))), dim3(256),
+                     0, cn::as_stream(stream), reinterpret_cast<const float4*>(raw_compact), sample_index, count,
+                     static_cast<int>(n_rows_max), raw, static_cast<int>(n_slots));
   return cn::launch_status();
 }
 

@@ -512,6 +512,52 @@ int cn_weight_cull(const float* weights, const float* ro, const float* rd, const
 int cn_scatter_rgb(const float* raw_compact, const int32_t* sample_index, int64_t n_rows, float* raw,
                    int64_t n_slots, cn_stream_t stream);
 
+/* --- Counted field calls: the row count in device memory (inference) ------
+ * cn_occupancy_cull and cn_weight_cull leave M' in device memory, and the calls above over their compact
+ * rows take it as a host integer: a caller must read it back, which synchronises the host and keeps the
+ * render out of a captured graph.  The counted entries take the CAPACITY n_rows_max of the compact
+ * buffers (n_rays * n_samples of the cull) and `count`, a device int64, 8-byte aligned -- the cull's.
+ * The launch is sized by the capacity and the kernel reads count[0] when it runs, so a graph replay
+ * follows the count of its own cull.  Let k = min(max(count[0], 0), n_rows_max):
+ *   rows j < k of every output hold exactly the bits the uncounted entry computes for rows 0 .. k-1 with
+ *     n_rays = chunk_rows = k (inside the kernel n_rays = chunk_rows = n_rows_max: with one sample per
+ *     row the Q1 ray of row j is j for any chunk_rows >= n_rays, in the folded decode too);
+ *   rows j >= k of every output are not written;
+ *   rows j >= k of every input (pts, rd, code_index, sample_index, raw_compact) may hold anything, NaN
+ *     and out-of-range code_index values included: they influence nothing, and no address is formed
+ *     from them (a partial tile's idle lanes repeat row k - 1; with k = 0 no row is decoded at all).
+ * Each is one launch on `stream`, without synchronisation or atomics; count[0] must not change between
+ * the launch and its completion other than by work ordered before it on the stream.
+ * The three field entries: fp32 16x16x4 kernels only -- cn_radiance_field_counted and
+ * cn_density_field_counted take CN_FMT_F32_W16, cn_radiance_field_fold_counted CN_FMT_F32_W16_FOLD -- in
+ * the points form: pts (n_rows_max, 3), n_samples = 1, for the radiance entries rd (n_rows_max, 3) the
+ * rows' own view directions (cn_occupancy_cull's vdir); one code row (n_codes = 1) or code_index
+ * (n_rows_max).  ro, z (and the density entry's rd) are in the signature as in the parents' and must
+ * be NULL.  Every other argument is the parent's.
+ * CN_EINVAL before any launch: count NULL or not 8-byte aligned; n_samples != 1; ro or z given; pts NULL;
+ * n_rows_max <= 0; any other format; neither code_index nor n_codes = 1; and the parent's pointer and
+ * alignment rules. */
+int cn_radiance_field_counted(const float* packed, int fmt, const float* code_bias, const int64_t* code_index,
+                              int64_t n_codes, const float* pts, const float* ro, const float* rd, const float* z,
+                              int64_t n_rows_max, int64_t n_samples, const int64_t* count, const float* freqs_xyz,
+                              const float* freqs_dir, float* raw, cn_stream_t stream);
+int cn_radiance_field_fold_counted(const float* packed, int fmt, const float* code_bias, const float* fold_bias,
+                                   const int64_t* code_index, int64_t n_codes, const float* pts, const float* ro,
+                                   const float* rd, const float* z, int64_t n_rows_max, int64_t n_samples,
+                                   const int64_t* count, const float* freqs_xyz, const float* freqs_dir, float* raw,
+                                   cn_stream_t stream);
+int cn_density_field_counted(const float* packed, int fmt, const float* code_bias, const int64_t* code_index,
+                             int64_t n_codes, const float* pts, const float* ro, const float* rd, const float* z,
+                             int64_t n_rows_max, int64_t n_samples, const int64_t* count, const float* freqs_xyz,
+                             float* sigma, float* raw, cn_stream_t stream);
+
+/* cn_scatter_rgb with n_rows = k of the rule above: raw_compact (n_rows_max, 4), sample_index
+ * (n_rows_max); the indices in rows >= k are not read.  One launch over n_rows_max rows.
+ * CN_EINVAL: a pointer NULL; count not 8-byte aligned; n_rows_max outside 1..n_slots; n_slots >
+ * INT32_MAX; raw_compact or raw not 16-byte aligned. */
+int cn_scatter_rgb_counted(const float* raw_compact, const int32_t* sample_index, const int64_t* count,
+                           int64_t n_rows_max, float* raw, int64_t n_slots, cn_stream_t stream);
+
 /* --- Scene composition (inference) --------------------------------------
  * Several posed objects in one image.  A rigid pose keeps the ray parameter -- the world point
  * ro + z rd is ro' + z rd' in the object's frame (cn_object_rays) -- so every object is sampled at the
