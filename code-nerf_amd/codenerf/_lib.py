@@ -131,6 +131,14 @@ SIGNATURES = {
                                                ctypes.POINTER(_p), _p, _i, _p]),
     "cn_object_rays_backward_workspace_floats": (_i64, [_i64, _i]),
     "cn_object_rays_backward": (_i, [_p, _p, _p, _p, _i64, _fp, _i, _p, _p, _i, _p, _p, _p]),
+    "cn_object_rays_scaled": (_i, [_p, _p, _i64, _fp, _i, _p, _p, _p]),
+    "cn_volume_render_compose_scaled": (_i, [ctypes.POINTER(_p), _fp, _i, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p,
+                                             _p]),
+    "cn_volume_render_compose_scaled_backward_workspace_floats": (_i64, [_i64, _i64, _i]),
+    "cn_volume_render_compose_scaled_backward": (_i, [ctypes.POINTER(_p), _fp, _i, _p, _p, _i64, _i64, _p, _p, _p, _p,
+                                                      _p, _p, ctypes.POINTER(_p), _p, _i, _p, _p, _p]),
+    "cn_object_rays_scaled_backward_workspace_floats": (_i64, [_i64, _i]),
+    "cn_object_rays_scaled_backward": (_i, [_p, _p, _p, _p, _i64, _fp, _i, _p, _p, _i, _p, _p, _p]),
     "cn_occupancy_gather": (_i, [_p, _p, _i64, _i64, _p, _p]),
     "cn_occupancy_cull_backward": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "cn_isosurface_workspace_bytes": (_i64, [_i64]),

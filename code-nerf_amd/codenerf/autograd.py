@@ -352,9 +352,9 @@ def _c(t):
 
 class ObjectRays(torch.autograd.Function):
     """ops.object_rays: world rays in every posed object's frame -> ro, rd (K, R, 3); gradients w.r.t. the world
-    rays and the poses (K, 12) (R row-major, then t).  cn_object_rays takes host poses: ``rows`` (K rows of 12
-    host floats) when the caller has them, else the pose tensor is read back -- ONE HOST SYNCHRONISATION per
-    render."""
+    rays and the poses (K, 12) (R row-major, then t) or (K, 13) (similarity poses: the scale last).
+    cn_object_rays takes host poses: ``rows`` (K rows of 12 or 13 host floats, as wide as ``poses``) when the
+    caller has them, else the pose tensor is read back -- ONE HOST SYNCHRONISATION per render."""
 
     @staticmethod
     def forward(ctx, ro, rd, poses, rows):
@@ -418,27 +418,40 @@ class ExpandRows(torch.autograd.Function):
 
 class VolumeRenderCompose(torch.autograd.Function):
     """ops.volume_render_compose -> rgb, disp, acc, weights, depth, acc_objects; gradients w.r.t. every object's
-    raw rows and rd (ops.volume_render_compose_backward)."""
+    raw rows and rd (ops.volume_render_compose_backward).  ``scales``: None, or the objects' uniform scales as a
+    (K,) tensor whose gradient is d_scales, with ``scale_rows`` their K host values (the caller's pose read-back
+    has them; without it the tensor is read back here: a host synchronisation)."""
 
     @staticmethod
-    def forward(ctx, z, rd, *raws):
+    def forward(ctx, z, rd, scales, scale_rows, *raws):
         ctx.set_materialize_grads(False)
+        if scales is not None and scale_rows is None:
+            scale_rows = scales.detach().cpu().tolist()
+        ctx.scale_rows = scale_rows
         ctx.save_for_backward(z, rd, *raws)
-        return ops.volume_render_compose(raws, z, rd)
+        return ops.volume_render_compose(raws, z, rd, scales=scale_rows)
 
     @staticmethod
     def backward(ctx, g_rgb, g_disp, g_acc, g_w, g_depth, g_ao):
         z, rd, *raws = ctx.saved_tensors
         if all(g is None for g in (g_rgb, g_disp, g_acc, g_w, g_depth, g_ao)):
-            return (None,) * (2 + len(raws))
+            return (None,) * (4 + len(raws))
+        needs = ctx.needs_input_grad
+        if ctx.scale_rows is not None and needs[2]:
+            d_raws, d_rd, d_scales = ops.volume_render_compose_backward(
+                raws, z, rd, _c(g_rgb), _c(g_disp), _c(g_acc), _c(g_w), _c(g_depth), _c(g_ao), want_rd=needs[1],
+                scales=ctx.scale_rows, want_scales=True)
+            return (None, d_rd, d_scales, None, *d_raws)
         d_raws, d_rd = ops.volume_render_compose_backward(raws, z, rd, _c(g_rgb), _c(g_disp), _c(g_acc), _c(g_w),
-                                                          _c(g_depth), _c(g_ao), want_rd=ctx.needs_input_grad[1])
-        return (None, d_rd, *d_raws)
+                                                          _c(g_depth), _c(g_ao), want_rd=needs[1],
+                                                          scales=ctx.scale_rows)
+        return (None, d_rd, None, None, *d_raws)
 
 
 def object_rays_autograd(ro, rd, poses=None, rows=None):
-    """World rays in K objects' frames -> ro, rd (K, R, 3).  ``poses``: a (K, 12) device tensor (read to the
-    host: a synchronisation), or None with ``rows``, K host rows of 12 floats."""
+    """World rays in K objects' frames -> ro, rd (K, R, 3).  ``poses``: a (K, 12) or (K, 13) device tensor (read
+    to the host: a synchronisation, unless ``rows`` holds its values already), or None with ``rows``, K host rows
+    of 12 or 13 floats."""
     if not _needs_grad(ro, rd, poses):
         if rows is None:
             rows = poses.detach().cpu().tolist()
@@ -469,10 +482,14 @@ def culled_field_autograd(model, ro, rd, z, z_s, z_t, occupancy, fx, fd):
     return ExpandRows.apply(raw, holder)
 
 
-def volume_render_compose_autograd(raws, z, rd):
-    if not _needs_grad(rd, *raws):
-        return ops.volume_render_compose([r.detach() for r in raws], z.detach(), rd.detach())
-    return VolumeRenderCompose.apply(z.detach(), rd, *raws)
+def volume_render_compose_autograd(raws, z, rd, scales=None, scale_rows=None):
+    """``scales``: the objects' scales as a (K,) tensor (differentiated), with or without their host values
+    ``scale_rows``; or None with ``scale_rows``, host constants; or neither: rigid poses."""
+    if not _needs_grad(rd, scales, *raws):
+        if scales is not None and scale_rows is None:
+            scale_rows = scales.detach().cpu().tolist()
+        return ops.volume_render_compose([r.detach() for r in raws], z.detach(), rd.detach(), scales=scale_rows)
+    return VolumeRenderCompose.apply(z.detach(), rd, scales, scale_rows, *raws)
 
 
 # ------------------------------------------------------------------ field

@@ -26,7 +26,8 @@ from .volumetric_render import volume_render
 __all__ = ["RaySampler", "PointSampler", "PositionalEmbedder", "volume_render", "prepare_samplers",
            "prepare_embedders", "predict_radiance_and_render", "forward_pass", "parallel_image_render",
            "render_rays", "gather_rows", "gather_views", "density", "density_grid", "OccupancyGrid", "Mesh", "extract_mesh",
-           "density_gradient", "normals", "SceneObject", "render_scene", "render_scene_autograd", "rigid_pose"]
+           "density_gradient", "normals", "SceneObject", "render_scene", "render_scene_autograd", "rigid_pose",
+           "similarity_pose"]
 
 
 def prepare_samplers(cfg, height: int, width: int, intrinsics, datatype, device) -> Tuple[RaySampler, PointSampler]:
@@ -668,15 +669,19 @@ def render_rays(ro: torch.Tensor, rd: torch.Tensor, z_s: torch.Tensor, z_t: torc
 
 class SceneObject:
     """One instance in a scene (render_scene): its codes ``z_s`` / ``z_t`` (one row each), its
-    OccupancyGrid in the object's own frame, and its rigid pose, the object-to-world ``rotation`` (3, 3) and
-    ``translation`` (3,) -- host values (nested sequences or CPU tensors), the identity by default.
+    OccupancyGrid in the object's own frame, and its similarity pose, the object-to-world ``rotation`` (3, 3),
+    ``translation`` (3,) and uniform ``scale`` -- host values (nested sequences or CPU tensors; a float), the
+    identity at scale 1 by default.
     The grid is mandatory (``OccupancyGrid.full`` is the minimum): a field means nothing outside the region
-    it was trained on and contributes exactly nothing there.  Uniform scale is not a pose: it would
-    rescale the densities.  ``coarse_model`` / ``fine_model``: this object's category models, the
-    scene's by default."""
+    it was trained on and contributes exactly nothing there.  ``scale``: how many times larger than its
+    canonical (unit-cube) size the object appears, finite and > 0.  It is kept apart from ``rotation``, which
+    stays orthonormal: an enlarged medium has its densities divided by the scale, so that the opacity along a
+    chord through the object does not depend on its size (include/codenerf.h's rule), and the object-frame
+    rays are divided by it, which keeps the ray parameter.  ``coarse_model`` / ``fine_model``: this object's
+    category models, the scene's by default."""
 
     def __init__(self, z_s: torch.Tensor, z_t: torch.Tensor, occupancy: OccupancyGrid, rotation=None, translation=None,
-                 coarse_model=None, fine_model=None):
+                 coarse_model=None, fine_model=None, scale: float = 1.0):
         if not isinstance(occupancy, OccupancyGrid):
             raise ValueError("a scene object needs its OccupancyGrid (OccupancyGrid.full(...) at the least): it "
                              "bounds the region the object's field is evaluated in")
@@ -690,14 +695,20 @@ class SceneObject:
         gram = max(abs(sum(rot[k][i] * rot[k][j] for k in range(3)) - (1.0 if i == j else 0.0))
                    for i in range(3) for j in range(3))
         if gram > 1e-5:
-            raise ValueError(f"rotation must be orthonormal (max |R^T R - I| = {gram:.3g} > 1e-5): a scene pose is "
-                             "rigid, scale would rescale the densities")
+            raise ValueError(f"rotation must be orthonormal (max |R^T R - I| = {gram:.3g} > 1e-5): a uniform size "
+                             "goes in scale=, which rescales the densities with it")
+        try:
+            scale = float(scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"scale must be one host number, got {scale!r}") from None
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"scale must be finite and > 0, got {scale}")
         for name, code in (("z_s", z_s), ("z_t", z_t)):
             if code.dim() != 2 or (code.shape[0] != 1 and code.stride(0) != 0):
                 raise ValueError(f"{name} must be one code row (1, C) (or an expand() of one)")
         self.codes = (z_s, z_t)                     # as given: what render_scene's gradient check looks at
         self.z_s, self.z_t = (c if c.shape[0] == 1 else c[:1] for c in self.codes)
-        self.occupancy, self.rotation, self.translation = occupancy, rot, t
+        self.occupancy, self.rotation, self.translation, self.scale = occupancy, rot, t, scale
         self.coarse_model, self.fine_model = coarse_model, fine_model
 
 
@@ -706,13 +717,15 @@ def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: Poi
                  t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
                  span_probes: Optional[int] = None, sync_free: bool = False) -> Dict[str, torch.Tensor]:
     """Several posed objects (1..8 SceneObjects) in one image: render_rays' hierarchical render of the world
-    rays ``ro`` / ``rd`` (R, 3), with the objects composed per sample.  A rigid pose keeps the ray
-    parameter, so one set of depths along the world ray serves every object: the coarse depths
+    rays ``ro`` / ``rd`` (R, 3), with the objects composed per sample.  A pose (rigid, or with a uniform scale:
+    the object-frame ray divided by it) keeps the ray parameter, so one set of depths along the world ray serves
+    every object: the coarse depths
     (ops.sample_uniform), each object's field on its own object-frame rays (ops.object_rays) under its grid
     (the density kernel when ``coarse_rgb=False``), ops.volume_render_compose with the world ``rd``,
     ops.sample_pdf on the composed weights, the objects' fine fields at the shared fine depths and the
     composition again.  Interpenetrating objects and partial transmittance are integrated as one medium
-    (include/codenerf.h's rule), not blended per image.
+    (include/codenerf.h's rule), not blended per image.  An object of scale s has its densities divided by s (the
+    scaled entries, taken when any object's scale is not 1; all scales 1 is the rigid render, bit for bit).
     Returns render_rays' entries plus "acc_objects_coarse" / "acc_objects_fine" (K, R): each object's share
     of "acc_*", its instance mask.  A sample's view direction is its own ray's (``chunk_rows`` is the whole
     ray list).  With one identity-posed object every shared entry is bitwise
@@ -749,7 +762,9 @@ def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: Poi
         if span_probes is None:
             _, z_c = ops.sample_uniform(ro, rd, ps.z_vals, ps.lower, ps.upper, t_rand if ps.perturb else None,
                                         want_pts=False)
-        ro_k, rd_k = ops.object_rays(ro, rd, [(o.rotation, o.translation) for o in objects])
+        scales = [o.scale for o in objects] if any(o.scale != 1.0 for o in objects) else None
+        ro_k, rd_k = ops.object_rays(ro, rd, [(o.rotation, o.translation) + (() if scales is None else (o.scale,))
+                                              for o in objects])
         if span_probes is not None:
             z_c, ray_span, probe_range = ps.sample_span(ro_k, rd_k, [o.occupancy for o in objects], t_rand,
                                                         span_probes)
@@ -760,7 +775,7 @@ def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: Poi
                     for k, (o, m) in enumerate(zip(objects, models))]
 
         rgb_c, disp_c, acc_c, w_c, depth_c, obj_c = ops.volume_render_compose(fields(coarse_models, z_c, not coarse_rgb),
-                                                                             z_c, rd)
+                                                                             z_c, rd, scales=scales)
         out = {"rgb_coarse": rgb_c, "disp_coarse": disp_c, "acc_coarse": acc_c, "weights_coarse": w_c,
                "depth_coarse": depth_c, "z_coarse": z_c, "acc_objects_coarse": obj_c}
         if not coarse_rgb:
@@ -773,7 +788,8 @@ def render_scene(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: Poi
             u = torch.rand(n, ps.num_samples_fine, dtype=torch.float32, device=ro.device)
         _, z_f = ops.sample_pdf(ro, rd, w_c[..., 1:-1], z_c, ps.num_samples_fine, u if ps.perturb else ps.u_lin,
                                 want_pts=False)
-        rgb_f, disp_f, acc_f, _, depth_f, obj_f = ops.volume_render_compose(fields(fine_models, z_f, False), z_f, rd)
+        rgb_f, disp_f, acc_f, _, depth_f, obj_f = ops.volume_render_compose(fields(fine_models, z_f, False), z_f, rd,
+                                                                           scales=scales)
         out.update({"rgb_fine": rgb_f, "disp_fine": disp_f, "acc_fine": acc_f, "depth_fine": depth_f, "z_fine": z_f,
                     "acc_objects_fine": obj_f})
     return out
@@ -800,6 +816,15 @@ def rigid_pose(omega: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
     return torch.cat([rot.reshape(9), t])
 
 
+def similarity_pose(omega: torch.Tensor, t: torch.Tensor, log_scale: torch.Tensor) -> torch.Tensor:
+    """A similarity pose from 7 numbers: ``rigid_pose(omega, t)`` and the uniform scale exp(``log_scale``) (a
+    scalar or (1,) tensor) -> (13,), a row of render_scene_autograd's (K, 13) ``poses``.  Plain torch ops,
+    differentiable; the exponential keeps the scale > 0 under any optimiser step."""
+    if log_scale.numel() != 1:
+        raise ValueError("log_scale must hold one number")
+    return torch.cat([rigid_pose(omega, t), log_scale.reshape(1).exp()])
+
+
 def render_scene_autograd(ro: torch.Tensor, rd: torch.Tensor, objects, point_sampler: PointSampler, embedders,
                           coarse_model, fine_model=None, *, poses: Optional[torch.Tensor] = None,
                           coarse_only: bool = False, t_rand: Optional[torch.Tensor] = None,
@@ -808,7 +833,10 @@ def render_scene_autograd(ro: torch.Tensor, rd: torch.Tensor, objects, point_sam
     gradients w.r.t. every object's ``z_s`` / ``z_t``, the world rays ``ro`` / ``rd`` and ``poses`` -- so a scene
     can be fitted to an image or to per-instance masks ("acc_objects_*").  ``poses``: an optional (K, 12) float32
     device tensor that overrides the objects' host poses, each row the object-to-world rotation row-major, then
-    the translation (``rigid_pose`` builds one from 6 numbers); it is read to the host once per render, one host
+    the translation (``rigid_pose`` builds one from 6 numbers); or (K, 13), each row with the object's uniform scale
+    last (``similarity_pose``), whose gradient is the sum of its two paths: through the object-frame rays and
+    through the densities.  With (K, 12) or None the objects' host scales are used, as constants.  The tensor is
+    read to the host once per render (the scales' host values come from the same read), one host
     synchronisation more than render_scene's 2 K (there is no ``sync_free`` here: the backward sizes its buffers
     by the kept counts).
     The path per object and pass: autograd.CullRows -> the fused fp32 field in points mode over the kept rows
@@ -832,12 +860,25 @@ def render_scene_autograd(ro: torch.Tensor, rd: torch.Tensor, objects, point_sam
         if getattr(_unwrap(m), "precision", "f32") != "f32":
             raise ValueError(f"render_scene_autograd runs the fp32 field (precision \"f32\"), got "
                              f"{_unwrap(m).precision!r}")
-    rows = None
+    rows = scales = scale_rows = None
+    host_scales = [o.scale for o in objects] if any(o.scale != 1.0 for o in objects) else None
     if poses is None:
-        rows = [[v for row in o.rotation for v in row] + list(o.translation) for o in objects]
-    elif not (isinstance(poses, torch.Tensor) and poses.shape == (len(objects), 12) and poses.dtype == torch.float32
-              and poses.device == ro.device):
-        raise ValueError(f"poses must be a ({len(objects)}, 12) float32 tensor on the rays' device")
+        rows = [[v for row in o.rotation for v in row] + list(o.translation) + ([] if host_scales is None else [o.scale])
+                for o in objects]
+        scale_rows = host_scales
+    elif not (isinstance(poses, torch.Tensor) and poses.dim() == 2 and poses.shape[0] == len(objects)
+              and poses.shape[1] in (12, 13) and poses.dtype == torch.float32 and poses.device == ro.device):
+        raise ValueError(f"poses must be a ({len(objects)}, 12) or ({len(objects)}, 13) float32 tensor on the rays' "
+                         "device")
+    elif poses.shape[1] == 13:
+        rows = poses.detach().cpu().tolist()            # the render's one pose read-back: the scales' host values too
+        scales, scale_rows = poses[:, 12], [row[12] for row in rows]
+        if not all(0.0 < v < float("inf") for v in scale_rows):
+            raise ValueError(f"every scale (poses[:, 12]) must be finite and > 0, got {scale_rows}")
+    elif host_scales is not None:
+        # rigid rows with the objects' constant scales: one (K, 13) tensor, no gradient into its last column
+        poses = torch.cat([poses, poses.new_tensor(host_scales)[:, None]], dim=1)
+        scale_rows = host_scales
     fx, fd = _check_embedders(embedders)
     n = ro.shape[0]
     ps = point_sampler
@@ -851,7 +892,8 @@ def render_scene_autograd(ro: torch.Tensor, rd: torch.Tensor, objects, point_sam
         return [culled_field_autograd(_unwrap(m), ro_k[k], rd_k[k], z, o.z_s, o.z_t, o.occupancy, fx, fd)
                 for k, (o, m) in enumerate(zip(objects, models))]
 
-    rgb_c, disp_c, acc_c, w_c, depth_c, obj_c = volume_render_compose_autograd(fields(coarse_models, z_c), z_c, rd)
+    rgb_c, disp_c, acc_c, w_c, depth_c, obj_c = volume_render_compose_autograd(fields(coarse_models, z_c), z_c, rd,
+                                                                                  scales, scale_rows)
     out = {"rgb_coarse": rgb_c, "disp_coarse": disp_c, "acc_coarse": acc_c, "weights_coarse": w_c,
            "depth_coarse": depth_c, "z_coarse": z_c, "acc_objects_coarse": obj_c}
     if coarse_only:
@@ -860,7 +902,8 @@ def render_scene_autograd(ro: torch.Tensor, rd: torch.Tensor, objects, point_sam
         u = torch.rand(n, ps.num_samples_fine, dtype=torch.float32, device=ro.device)
     _, z_f = ops.sample_pdf(ro.detach(), rd.detach(), w_c.detach()[..., 1:-1], z_c, ps.num_samples_fine,
                             u if ps.perturb else ps.u_lin, want_pts=False)
-    rgb_f, disp_f, acc_f, _, depth_f, obj_f = volume_render_compose_autograd(fields(fine_models, z_f), z_f, rd)
+    rgb_f, disp_f, acc_f, _, depth_f, obj_f = volume_render_compose_autograd(fields(fine_models, z_f), z_f, rd,
+                                                                                scales, scale_rows)
     out.update({"rgb_fine": rgb_f, "disp_fine": disp_f, "acc_fine": acc_f, "depth_fine": depth_f, "z_fine": z_f,
                 "acc_objects_fine": obj_f})
     return out

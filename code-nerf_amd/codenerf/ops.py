@@ -351,16 +351,28 @@ def volume_render(raw: Tensor, z: Tensor, rd: Tensor, want_weights: bool = True)
     return rgb, disp, acc, w, depth
 
 
+def _scale_values(scales, k: int) -> list:
+    """K uniform scales as host floats, each finite and > 0."""
+    vals = [float(v) for v in scales]
+    assert len(vals) == k, f"scales must hold one value per object ({k}), got {len(vals)}"
+    assert all(v > 0.0 and v != float("inf") for v in vals), f"every scale must be finite and > 0, got {vals}"
+    return vals
+
+
 def volume_render_compose(raws: Sequence[Tensor], z: Tensor, rd: Tensor, want_weights: bool = True,
-                          want_acc_objects: bool = True):
+                          want_acc_objects: bool = True, scales=None):
     """Several objects' raw rows at the same depths as one ray integral (cn_volume_render_compose; the rule
     is in include/codenerf.h): ``raws`` 1..8 tensors (R, S, 4), ``z`` (R, S), the world ``rd`` (R, 3) ->
     rgb, disp, acc, weights, depth as volume_render, and acc_objects (K, R): each object's share of acc, its
-    instance mask.  One object gives volume_render's bits."""
+    instance mask.  One object gives volume_render's bits.  ``scales``: K host floats, the objects' uniform
+    scales (cn_volume_render_compose_scaled: object k's density is divided by scales[k]); all 1 gives the
+    unscaled bits."""
     lib = _lib_ready()
     raws = list(raws)
     assert 1 <= len(raws) <= _lib.CN_MAX_SCENE_OBJECTS, \
         f"a scene holds 1..{_lib.CN_MAX_SCENE_OBJECTS} objects, got {len(raws)}"
+    if scales is not None:
+        scales = _scale_values(scales, len(raws))
     z, rd = _aligned16(_cuda(z, "depth_values")), _cuda(rd, "ray_directions")
     n, s = z.shape
     raws = [_aligned16(_cuda(raw, f"raws[{k}]")) for k, raw in enumerate(raws)]
@@ -376,50 +388,66 @@ def volume_render_compose(raws: Sequence[Tensor], z: Tensor, rd: Tensor, want_we
     acc_objects = torch.empty(len(raws), n, device=dev, dtype=torch.float32) if want_acc_objects else None
     if n:
         pointers, keep = _lib.pointer_array(raws)
-        check(lib.cn_volume_render_compose(pointers, len(raws), ptr(z), ptr(rd), n, s, ptr(rgb), ptr(disp), ptr(acc),
-                                           ptr(w), ptr(depth), ptr(acc_objects), stream_of(z)),
-              "cn_volume_render_compose")
+        if scales is None:
+            check(lib.cn_volume_render_compose(pointers, len(raws), ptr(z), ptr(rd), n, s, ptr(rgb), ptr(disp),
+                                               ptr(acc), ptr(w), ptr(depth), ptr(acc_objects), stream_of(z)),
+                  "cn_volume_render_compose")
+        else:
+            check(lib.cn_volume_render_compose_scaled(pointers, _lib.host_floats(scales), len(raws), ptr(z), ptr(rd), n,
+                                                      s, ptr(rgb), ptr(disp), ptr(acc), ptr(w), ptr(depth),
+                                                      ptr(acc_objects), stream_of(z)),
+                  "cn_volume_render_compose_scaled")
         del keep
     if w is not None and s == 1:
         w = w[:, :0]          # as volume_render: the reference's S == 1 weights are (R, 0)
     return rgb, disp, acc, w, depth, acc_objects
 
 
-def _pose_rows(poses) -> list:
-    """K poses as 12 K host floats: each a (rotation (3, 3), translation (3,)) pair or a row of 12 (R row-major,
-    then t)."""
+def _pose_rows(poses) -> Tuple[list, int]:
+    """K poses as host floats and their width: each a (rotation (3, 3), translation (3,)) pair or a row of 12 (R
+    row-major, then t) -- width 12 -- or a (rotation, translation, scale) triple or a row of 13 -- width 13, a
+    similarity pose; with any of these every pose becomes 13 floats (a rigid one gets scale 1)."""
     poses = list(poses)
     assert 1 <= len(poses) <= _lib.CN_MAX_SCENE_OBJECTS, \
         f"a scene holds 1..{_lib.CN_MAX_SCENE_OBJECTS} objects, got {len(poses)}"
-    flat = []
+    all_rows = []
     for pose in poses:
         pose = list(pose)
-        if len(pose) == 2:
-            rot, t = pose
+        if len(pose) in (2, 3):
+            rot, t = pose[:2]
             rows = [float(v) for row in rot for v in row] + [float(v) for v in t]
+            assert len(rows) == 12, "a pose is a (3, 3) rotation and a (3,) translation"
+            rows += [float(pose[2])] if len(pose) == 3 else []
         else:
             rows = [float(v) for v in pose]
-        assert len(rows) == 12, "a pose is a (3, 3) rotation and a (3,) translation"
-        flat += rows
-    return flat
+        assert len(rows) in (12, 13), "a pose is a (3, 3) rotation, a (3,) translation and an optional scale"
+        all_rows.append(rows)
+    width = max(len(rows) for rows in all_rows)
+    flat = [v for rows in all_rows for v in rows + [1.0] * (width - len(rows))]
+    if width == 13:
+        _scale_values(flat[12::13], len(poses))
+    return flat, width
 
 
 def object_rays(ro: Tensor, rd: Tensor, poses) -> Tuple[Tensor, Tensor]:
     """World rays (R, 3) in the frames of K posed objects (cn_object_rays) -> ro (K, R, 3), rd (K, R, 3).
     ``poses``: K host (rotation (3, 3) row-major object-to-world, translation (3,)) pairs of floats, or K rows of
     12 (the rotation row-major, then the translation); the ray parameter is unchanged, so ro[k] + z rd[k] is the
-    world point ro + z rd in object k's frame."""
+    world point ro + z rd in object k's frame.  (rotation, translation, scale) triples or rows of 13 are similarity
+    poses (cn_object_rays_scaled): the object-frame rays are divided by the scale, the ray parameter still
+    unchanged; scale 1 gives the rigid pose's bits."""
     lib = _lib_ready()
     ro, rd = _cuda(ro, "ro"), _cuda(rd, "rd")
     n = ro.shape[0]
     assert ro.shape == (n, 3) and rd.shape == (n, 3), "ro / rd must be (num_rays, 3)"
-    flat = _pose_rows(poses)
-    k = len(flat) // 12
+    flat, width = _pose_rows(poses)
+    k = len(flat) // width
     ro_out = torch.empty(k, n, 3, device=ro.device, dtype=torch.float32)
     rd_out = torch.empty(k, n, 3, device=ro.device, dtype=torch.float32)
     if n:
-        check(lib.cn_object_rays(ptr(ro), ptr(rd), n, _lib.host_floats(flat), k, ptr(ro_out), ptr(rd_out),
-                                 stream_of(ro)), "cn_object_rays")
+        entry, name = ((lib.cn_object_rays, "cn_object_rays") if width == 12 else
+                       (lib.cn_object_rays_scaled, "cn_object_rays_scaled"))
+        check(entry(ptr(ro), ptr(rd), n, _lib.host_floats(flat), k, ptr(ro_out), ptr(rd_out), stream_of(ro)), name)
     return ro_out, rd_out
 
 
@@ -1066,14 +1094,20 @@ def volume_render_backward(raw: Tensor, z: Tensor, rd: Tensor, g_rgb=None, g_dis
 
 def volume_render_compose_backward(raws: Sequence[Tensor], z: Tensor, rd: Tensor, g_rgb=None, g_disp=None, g_acc=None,
                                    g_weights=None, g_depth=None, g_acc_objects=None, want_rd: bool = True,
-                                   d_rd_into: Optional[Tensor] = None) -> Tuple[list, Optional[Tensor]]:
+                                   d_rd_into: Optional[Tensor] = None, scales=None, want_scales: bool = False):
     """Gradient of volume_render_compose (cn_volume_render_compose_backward; the rule is in include/codenerf.h)
     -> (d_raws: one (R, S, 4) tensor per object, d_rd (R, 3) or None).  The upstream gradients as
-    volume_render_backward's, plus ``g_acc_objects`` (K, R); ``d_rd_into``: d rd ADDED into it and returned."""
+    volume_render_backward's, plus ``g_acc_objects`` (K, R); ``d_rd_into``: d rd ADDED into it and returned.
+    ``scales``: the forward's K host scales (cn_volume_render_compose_scaled_backward); with ``want_scales`` a
+    third result, d_scales (K,), the gradient w.r.t. the scales through the densities (a fixed reduction order:
+    two runs give the same bits)."""
     lib = _lib_ready()
     raws = list(raws)
     assert 1 <= len(raws) <= _lib.CN_MAX_SCENE_OBJECTS, \
         f"a scene holds 1..{_lib.CN_MAX_SCENE_OBJECTS} objects, got {len(raws)}"
+    assert scales is not None or not want_scales, "want_scales needs the forward's scales"
+    if scales is not None:
+        scales = _scale_values(scales, len(raws))
     z, rd = _aligned16(_cuda(z, "depth_values")), _cuda(rd, "ray_directions")
     n, s = z.shape
     raws = [_aligned16(_cuda(raw, f"raws[{k}]")) for k, raw in enumerate(raws)]
@@ -1095,31 +1129,43 @@ def volume_render_compose_backward(raws: Sequence[Tensor], z: Tensor, rd: Tensor
         d_rd = d_rd_into
     else:
         d_rd = torch.empty_like(rd) if want_rd else None
+    d_scales = torch.empty(len(raws), device=z.device, dtype=torch.float32) if want_scales else None
     if n == 0:      # no rays: empty gradients (the C ABI refuses n_rays == 0), as the forward
-        return d_raws, d_rd
+        return (d_raws, d_rd, d_scales.zero_()) if want_scales else (d_raws, d_rd)
     pointers, keep = _lib.pointer_array(raws)
     outs, keep_outs = _lib.pointer_array(d_raws)
-    check(lib.cn_volume_render_compose_backward(pointers, len(raws), ptr(z), ptr(rd), n, s, ptr(g_rgb), ptr(g_disp),
-                                                ptr(g_acc), ptr(g_weights), ptr(g_depth), ptr(g_acc_objects), outs,
-                                                ptr(d_rd), int(d_rd_into is not None), stream_of(z)),
-          "cn_volume_render_compose_backward")
+    if scales is None:
+        check(lib.cn_volume_render_compose_backward(pointers, len(raws), ptr(z), ptr(rd), n, s, ptr(g_rgb), ptr(g_disp),
+                                                    ptr(g_acc), ptr(g_weights), ptr(g_depth), ptr(g_acc_objects), outs,
+                                                    ptr(d_rd), int(d_rd_into is not None), stream_of(z)),
+              "cn_volume_render_compose_backward")
+    else:
+        workspace = None
+        if want_scales:
+            workspace = torch.empty(lib.cn_volume_render_compose_scaled_backward_workspace_floats(n, s, len(raws)),
+                                    device=z.device, dtype=torch.float32)
+        check(lib.cn_volume_render_compose_scaled_backward(
+            pointers, _lib.host_floats(scales), len(raws), ptr(z), ptr(rd), n, s, ptr(g_rgb), ptr(g_disp), ptr(g_acc),
+            ptr(g_weights), ptr(g_depth), ptr(g_acc_objects), outs, ptr(d_rd), int(d_rd_into is not None),
+            ptr(d_scales), ptr(workspace), stream_of(z)), "cn_volume_render_compose_scaled_backward")
     del keep, keep_outs
-    return d_raws, d_rd
+    return (d_raws, d_rd, d_scales) if want_scales else (d_raws, d_rd)
 
 
 def object_rays_backward(g_ro_obj: Optional[Tensor], g_rd_obj: Optional[Tensor], ro: Tensor, rd: Tensor, poses,
                          want_ro: bool = True, want_rd: bool = True, want_poses: bool = True,
                          ray_into: Optional[Tuple[Tensor, Tensor]] = None):
     """Gradient of object_rays (cn_object_rays_backward) -> (d_ro (R, 3), d_rd (R, 3), d_poses (K, 12): dR
-    row-major, then dt), each None when not wanted.  ``g_ro_obj`` / ``g_rd_obj`` (K, R, 3), either may be None
-    (zero); ``poses`` as object_rays takes them (or rows of 12).  ``ray_into``: (d_ro, d_rd) contiguous (R, 3)
-    device tensors the rays' gradients are ADDED into, and returned.  Deterministic: a fixed reduction order."""
+    row-major, then dt -- (K, 13) with the scale's gradient last for similarity poses,
+    cn_object_rays_scaled_backward), each None when not wanted.  ``g_ro_obj`` / ``g_rd_obj`` (K, R, 3), either may
+    be None (zero); ``poses`` as object_rays takes them.  ``ray_into``: (d_ro, d_rd) contiguous (R, 3) device
+    tensors the rays' gradients are ADDED into, and returned.  Deterministic: a fixed reduction order."""
     lib = _lib_ready()
     ro, rd = _cuda(ro, "ro"), _cuda(rd, "rd")
     n = ro.shape[0]
     assert ro.shape == (n, 3) and rd.shape == (n, 3), "ro / rd must be (num_rays, 3)"
-    flat = _pose_rows(poses)
-    k = len(flat) // 12
+    flat, width = _pose_rows(poses)
+    k = len(flat) // width
     g_ro_obj, g_rd_obj = _opt(g_ro_obj, "g_ro_obj"), _opt(g_rd_obj, "g_rd_obj")
     assert all(g is None or g.shape == (k, n, 3) for g in (g_ro_obj, g_rd_obj)), \
         "g_ro_obj / g_rd_obj must be (num_objects, num_rays, 3)"
@@ -1130,16 +1176,19 @@ def object_rays_backward(g_ro_obj: Optional[Tensor], g_rd_obj: Optional[Tensor],
     else:
         d_ro = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_ro else None
         d_rd = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_rd else None
-    d_poses = torch.empty(k, 12, device=dev, dtype=torch.float32) if want_poses else None
+    d_poses = torch.empty(k, width, device=dev, dtype=torch.float32) if want_poses else None
     assert d_ro is not None or d_rd is not None or d_poses is not None, "nothing wanted"
     if n == 0:
         return d_ro, d_rd, (None if d_poses is None else d_poses.zero_())
+    entry, floats, name = ((lib.cn_object_rays_backward, lib.cn_object_rays_backward_workspace_floats,
+                            "cn_object_rays_backward") if width == 12 else
+                           (lib.cn_object_rays_scaled_backward, lib.cn_object_rays_scaled_backward_workspace_floats,
+                            "cn_object_rays_scaled_backward"))
     workspace = None
     if want_poses:
-        workspace = torch.empty(lib.cn_object_rays_backward_workspace_floats(n, k), device=dev, dtype=torch.float32)
-    check(lib.cn_object_rays_backward(ptr(g_ro_obj), ptr(g_rd_obj), ptr(ro), ptr(rd), n, _lib.host_floats(flat), k,
-                                      ptr(d_ro), ptr(d_rd), int(ray_into is not None), ptr(d_poses), ptr(workspace),
-                                      stream_of(ro)), "cn_object_rays_backward")
+        workspace = torch.empty(floats(n, k), device=dev, dtype=torch.float32)
+    check(entry(ptr(g_ro_obj), ptr(g_rd_obj), ptr(ro), ptr(rd), n, _lib.host_floats(flat), k, ptr(d_ro), ptr(d_rd),
+                int(ray_into is not None), ptr(d_poses), ptr(workspace), stream_of(ro)), name)
     return d_ro, d_rd, d_poses
 
 

@@ -102,13 +102,35 @@ namespace {
 struct ObjectPoses {
   float p[CN_MAX_SCENE_OBJECTS][12];  // R row-major (object to world), then t
 };
+struct ObjectScales {
+  float s[CN_MAX_SCENE_OBJECTS];  // a similarity pose's 13th float (read by the SCALED instances only)
+};
+
+// Host poses of `stride` (12 or 13) floats each into the kernels' argument structs; false for an entry that is
+// not finite or a scale that is not > 0.
+inline bool read_poses(const float* poses, int n_objects, int stride, ObjectPoses& p, ObjectScales& sc) {
+  for (int k = 0; k < n_objects; ++k) {
+    for (int e = 0; e < 12; ++e) {
+      const float v = poses[stride * k + e];
+      if (!(v - v == 0.0f)) return false;  // finite
+      p.p[k][e] = v;
+    }
+    const float v = stride == 13 ? poses[13 * k + 12] : 1.0f;
+    if (!(v - v == 0.0f && v > 0.0f)) return false;
+    sc.s[k] = v;
+  }
+  return true;
+}
 
 // World rays in every object's frame: the inverse rigid map R^T (x - t), every operation rounded
-// (include/codenerf.h).  One lane per ray, the object is the block's y index.
+// (include/codenerf.h).  One lane per ray, the object is the block's y index.  SCALED: a similarity pose, the
+// result divided by the object's scale.
+template <bool SCALED>
 __global__ __launch_bounds__(256) void object_rays_kernel(const float* __restrict__ ro, const float* __restrict__ rd,
-                                                          int64_t n_rays, ObjectPoses poses,
+                                                          int64_t n_rays, ObjectPoses poses, ObjectScales scales,
                                                           float* __restrict__ ro_out, float* __restrict__ rd_out) {
   const int k = blockIdx.y;
+  const float sc = SCALED ? scales.s[k] : 1.0f;
   float m[12];
 #pragma unroll
   for (int e = 0; e < 12; ++e) m[e] = poses.p[k][e];
@@ -119,10 +141,10 @@ __global__ __launch_bounds__(256) void object_rays_kernel(const float* __restric
     const float v0 = rd[3 * r], v1 = rd[3 * r + 1], v2 = rd[3 * r + 2];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      ro_out[3 * q + i] =
-          __fadd_rn(__fadd_rn(__fmul_rn(d0, m[i]), __fmul_rn(d1, m[3 + i])), __fmul_rn(d2, m[6 + i]));
-      rd_out[3 * q + i] =
-          __fadd_rn(__fadd_rn(__fmul_rn(v0, m[i]), __fmul_rn(v1, m[3 + i])), __fmul_rn(v2, m[6 + i]));
+      const float uo = __fadd_rn(__fadd_rn(__fmul_rn(d0, m[i]), __fmul_rn(d1, m[3 + i])), __fmul_rn(d2, m[6 + i]));
+      const float uv = __fadd_rn(__fadd_rn(__fmul_rn(v0, m[i]), __fmul_rn(v1, m[3 + i])), __fmul_rn(v2, m[6 + i]));
+      ro_out[3 * q + i] = SCALED ? __fdiv_rn(uo, sc) : uo;
+      rd_out[3 * q + i] = SCALED ? __fdiv_rn(uv, sc) : uv;
     }
   }
 }
@@ -134,14 +156,22 @@ extern "C" int cn_object_rays(const float* ro, const float* rd, int64_t n_rays, 
   CN_CHECK_ARG(ro && rd && poses && ro_out && rd_out && n_rays > 0);
   CN_CHECK_ARG(n_objects >= 1 && n_objects <= CN_MAX_SCENE_OBJECTS);
   ObjectPoses p = {};
-  for (int k = 0; k < n_objects; ++k)
-    for (int e = 0; e < 12; ++e) {
-      const float v = poses[12 * k + e];
-      CN_CHECK_ARG(v - v == 0.0f);  // finite
-      p.p[k][e] = v;
-    }
-  hipLaunchKernelGGL(object_rays_kernel, dim3(cn::elementwise_grid(n_rays, 256), n_objects), dim3(256), 0,
-                     cn::as_stream(stream), ro, rd, n_rays, p, ro_out, rd_out);
+  ObjectScales sc = {};
+  CN_CHECK_ARG(read_poses(poses, n_objects, 12, p, sc));
+  hipLaunchKernelGGL(object_rays_kernel<false>, dim3(cn::elementwise_grid(n_rays, 256), n_objects), dim3(256), 0,
+                     cn::as_stream(stream), ro, rd, n_rays, p, sc, ro_out, rd_out);
+  return cn::launch_status();
+}
+
+extern "C" int cn_object_rays_scaled(const float* ro, const float* rd, int64_t n_rays, const float* poses,
+                                     int n_objects, float* ro_out, float* rd_out, cn_stream_t stream) {
+  CN_CHECK_ARG(ro && rd && poses && ro_out && rd_out && n_rays > 0);
+  CN_CHECK_ARG(n_objects >= 1 && n_objects <= CN_MAX_SCENE_OBJECTS);
+  ObjectPoses p = {};
+  ObjectScales sc = {};
+  CN_CHECK_ARG(read_poses(poses, n_objects, 13, p, sc));
+  hipLaunchKernelGGL(object_rays_kernel<true>, dim3(cn::elementwise_grid(n_rays, 256), n_objects), dim3(256), 0,
+                     cn::as_stream(stream), ro, rd, n_rays, p, sc, ro_out, rd_out);
   return cn::launch_status();
 }
 
@@ -228,7 +258,8 @@ extern "C" int cn_gather_rays_backward(const float* g_ro, const float* g_rd, int
 // gradients into the ray's d ro / d rd (one writer per element) and forms the ray's 12 pose terms per object;
 // a block's lanes walk the rays in a fixed stride, its 12 sums per object are reduced by the fixed LDS tree of
 // ray_bundle_backward_kernel into the workspace's block partials, and a second launch reduces the partials, one
-// block per object, in the same fixed order: no atomics, two runs give the same bits.
+// block per object, in the same fixed order: no atomics, two runs give the same bits.  cn_object_rays_scaled_backward
+// is the SCALED instance: the gradients divided by the object's scale first, and the scale's own sum as a 13th.
 namespace {
 
 constexpr int kPoseBlocks = 256;  // at most: block partials per object
@@ -237,26 +268,31 @@ inline int pose_blocks(int64_t n_rays) {
   return static_cast<int>(cn::ceil_div(n_rays, 256) < kPoseBlocks ? cn::ceil_div(n_rays, 256) : kPoseBlocks);
 }
 
-// The tree over the block's 256 lanes of 12 sums each -> out[0..12) (from lanes 0..11).
-__device__ __forceinline__ void reduce12(float (&red)[12][256], const float (&acc)[12], float* __restrict__ out) {
+// The tree over the block's 256 lanes of N sums each -> out[0..N) (from lanes 0..N-1).  N: 12 for a rigid
+// pose, 13 with the scale's sum.
+template <int N>
+__device__ __forceinline__ void reduce_sums(float (&red)[N][256], const float (&acc)[N], float* __restrict__ out) {
 #pragma unroll
-  for (int e = 0; e < 12; ++e) red[e][threadIdx.x] = acc[e];
+  for (int e = 0; e < N; ++e) red[e][threadIdx.x] = acc[e];
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
     if (threadIdx.x < s)
 #pragma unroll
-      for (int e = 0; e < 12; ++e) red[e][threadIdx.x] += red[e][threadIdx.x + s];
+      for (int e = 0; e < N; ++e) red[e][threadIdx.x] += red[e][threadIdx.x + s];
     __syncthreads();
   }
-  if (threadIdx.x < 12) out[threadIdx.x] = red[threadIdx.x][0];
+  if (threadIdx.x < N) out[threadIdx.x] = red[threadIdx.x][0];
   __syncthreads();  // red is rewritten by the next object
 }
 
+// SCALED: similarity poses -- the upstream gradients divided by the object's scale first, and a 13th sum.
+template <bool SCALED>
 __global__ __launch_bounds__(256) void object_rays_backward_kernel(
     const float* __restrict__ g_ro, const float* __restrict__ g_rd, const float* __restrict__ ro,
-    const float* __restrict__ rd, int64_t n_rays, ObjectPoses poses, int n_objects, float* __restrict__ d_ro,
-    float* __restrict__ d_rd, int accumulate, float* __restrict__ partials) {
-  __shared__ float red[12][256];
+    const float* __restrict__ rd, int64_t n_rays, ObjectPoses poses, ObjectScales scales, int n_objects,
+    float* __restrict__ d_ro, float* __restrict__ d_rd, int accumulate, float* __restrict__ partials) {
+  constexpr int N = SCALED ? 13 : 12;
+  __shared__ float red[N][256];
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int64_t first = blockIdx.x * (int64_t)256 + threadIdx.x;
   // the rays' own gradients: sum_k R_k g_k, ascending k
@@ -268,7 +304,11 @@ __global__ __launch_bounds__(256) void object_rays_backward_kernel(
         const int64_t q = 3 * (k * n_rays + r);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          const float go = g_ro ? g_ro[q + i] : 0.0f, gv = g_rd ? g_rd[q + i] : 0.0f;
+          float go = g_ro ? g_ro[q + i] : 0.0f, gv = g_rd ? g_rd[q + i] : 0.0f;
+          if constexpr (SCALED) {
+            go = __fdiv_rn(go, scales.s[k]);
+            gv = __fdiv_rn(gv, scales.s[k]);
+          }
 #pragma unroll
           for (int j = 0; j < 3; ++j) {
             so[j] += m[3 * j + i] * go;
@@ -286,9 +326,9 @@ __global__ __launch_bounds__(256) void object_rays_backward_kernel(
   if (!partials) return;  // uniform: no pose gradient wanted
   for (int k = 0; k < n_objects; ++k) {
     const float* m = poses.p[k];
-    float acc[12];
+    float acc[N];
 #pragma unroll
-    for (int e = 0; e < 12; ++e) acc[e] = 0.0f;
+    for (int e = 0; e < N; ++e) acc[e] = 0.0f;
     for (int64_t r = first; r < n_rays; r += stride) {
       const int64_t q = 3 * (k * n_rays + r);
       float go[3], gv[3];
@@ -296,6 +336,23 @@ __global__ __launch_bounds__(256) void object_rays_backward_kernel(
       for (int i = 0; i < 3; ++i) {
         go[i] = g_ro ? g_ro[q + i] : 0.0f;
         gv[i] = g_rd ? g_rd[q + i] : 0.0f;
+      }
+      if constexpr (SCALED) {
+        // the forward's outputs again (its expressions), against the gradients as they came; then g' = g / s
+        const float sc = scales.s[k];
+        const float e0 = __fsub_rn(ro[3 * r], m[9]), e1 = __fsub_rn(ro[3 * r + 1], m[10]);
+        const float e2 = __fsub_rn(ro[3 * r + 2], m[11]);
+        const float v0 = rd[3 * r], v1 = rd[3 * r + 1], v2 = rd[3 * r + 2];
+        float t = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const float uo = __fadd_rn(__fadd_rn(__fmul_rn(e0, m[i]), __fmul_rn(e1, m[3 + i])), __fmul_rn(e2, m[6 + i]));
+          const float uv = __fadd_rn(__fadd_rn(__fmul_rn(v0, m[i]), __fmul_rn(v1, m[3 + i])), __fmul_rn(v2, m[6 + i]));
+          t += __fdiv_rn(uo, sc) * go[i] + __fdiv_rn(uv, sc) * gv[i];
+          go[i] = __fdiv_rn(go[i], sc);
+          gv[i] = __fdiv_rn(gv[i], sc);
+        }
+        acc[12] -= t / sc;
       }
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
@@ -307,23 +364,24 @@ __global__ __launch_bounds__(256) void object_rays_backward_kernel(
         }
       }
     }
-    reduce12(red, acc, partials + ((int64_t)k * gridDim.x + blockIdx.x) * 12);
+    reduce_sums<N>(red, acc, partials + ((int64_t)k * gridDim.x + blockIdx.x) * N);
   }
 }
 
 // Stage 2, one block per object: lane t sums the block partials t, t + 256, ... (at most one with
 // kPoseBlocks = 256), then the tree.
+template <int N>
 __global__ __launch_bounds__(256) void object_poses_reduce_kernel(const float* __restrict__ partials, int n_blocks,
                                                                   float* __restrict__ d_poses) {
-  __shared__ float red[12][256];
+  __shared__ float red[N][256];
   const int k = blockIdx.x;
-  float acc[12];
+  float acc[N];
 #pragma unroll
-  for (int e = 0; e < 12; ++e) acc[e] = 0.0f;
+  for (int e = 0; e < N; ++e) acc[e] = 0.0f;
   for (int b = threadIdx.x; b < n_blocks; b += 256)
 #pragma unroll
-    for (int e = 0; e < 12; ++e) acc[e] += partials[((int64_t)k * n_blocks + b) * 12 + e];
-  reduce12(red, acc, d_poses + 12 * k);
+    for (int e = 0; e < N; ++e) acc[e] += partials[((int64_t)k * n_blocks + b) * N + e];
+  reduce_sums<N>(red, acc, d_poses + N * k);
 }
 
 }  // namespace
@@ -341,17 +399,38 @@ extern "C" int cn_object_rays_backward(const float* g_ro_obj, const float* g_rd_
   CN_CHECK_ARG(d_ro || d_rd || d_poses);
   CN_CHECK_ARG(!d_poses || workspace);
   ObjectPoses p = {};
-  for (int k = 0; k < n_objects; ++k)
-    for (int e = 0; e < 12; ++e) {
-      const float v = poses[12 * k + e];
-      CN_CHECK_ARG(v - v == 0.0f);  // finite
-      p.p[k][e] = v;
-    }
+  ObjectScales sc = {};
+  CN_CHECK_ARG(read_poses(poses, n_objects, 12, p, sc));
   const int blocks = pose_blocks(n_rays);
   hipStream_t st = cn::as_stream(stream);
-  hipLaunchKernelGGL(object_rays_backward_kernel, dim3(blocks), dim3(256), 0, st, g_ro_obj, g_rd_obj, ro, rd, n_rays, p,
-                     n_objects, d_ro, d_rd, accumulate, d_poses ? workspace : nullptr);
+  hipLaunchKernelGGL(object_rays_backward_kernel<false>, dim3(blocks), dim3(256), 0, st, g_ro_obj, g_rd_obj, ro, rd,
+                     n_rays, p, sc, n_objects, d_ro, d_rd, accumulate, d_poses ? workspace : nullptr);
   if (d_poses)
-    hipLaunchKernelGGL(object_poses_reduce_kernel, dim3(n_objects), dim3(256), 0, st, workspace, blocks, d_poses);
+    hipLaunchKernelGGL(object_poses_reduce_kernel<12>, dim3(n_objects), dim3(256), 0, st, workspace, blocks, d_poses);
+  return cn::launch_status();
+}
+
+extern "C" int64_t cn_object_rays_scaled_backward_workspace_floats(int64_t n_rays, int n_objects) {
+  if (n_rays <= 0 || n_objects < 1 || n_objects > CN_MAX_SCENE_OBJECTS) return -1;
+  return (int64_t)pose_blocks(n_rays) * n_objects * 13;
+}
+
+extern "C" int cn_object_rays_scaled_backward(const float* g_ro_obj, const float* g_rd_obj, const float* ro,
+                                              const float* rd, int64_t n_rays, const float* poses, int n_objects,
+                                              float* d_ro, float* d_rd, int accumulate, float* d_poses,
+                                              float* workspace, cn_stream_t stream) {
+  CN_CHECK_ARG(ro && rd && poses && n_rays > 0 && (accumulate == 0 || accumulate == 1));
+  CN_CHECK_ARG(n_objects >= 1 && n_objects <= CN_MAX_SCENE_OBJECTS);
+  CN_CHECK_ARG(d_ro || d_rd || d_poses);
+  CN_CHECK_ARG(!d_poses || workspace);
+  ObjectPoses p = {};
+  ObjectScales sc = {};
+  CN_CHECK_ARG(read_poses(poses, n_objects, 13, p, sc));
+  const int blocks = pose_blocks(n_rays);
+  hipStream_t st = cn::as_stream(stream);
+  hipLaunchKernelGGL(object_rays_backward_kernel<true>, dim3(blocks), dim3(256), 0, st, g_ro_obj, g_rd_obj, ro, rd,
+                     n_rays, p, sc, n_objects, d_ro, d_rd, accumulate, d_poses ? workspace : nullptr);
+  if (d_poses)
+    hipLaunchKernelGGL(object_poses_reduce_kernel<13>, dim3(n_objects), dim3(256), 0, st, workspace, blocks, d_poses);
   return cn::launch_status();
 }

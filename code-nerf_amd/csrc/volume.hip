@@ -424,10 +424,34 @@ namespace {
 struct ComposeRaws {
   const float* p[CN_MAX_SCENE_OBJECTS];
 };
+// The objects' uniform scales (cn_volume_render_compose_scaled): read by the SCALED instances only, whose
+// density is softplus20(xs - 1) / s_k; the others are the unscaled entries' kernels as they were.
+struct ComposeScales {
+  float s[CN_MAX_SCENE_OBJECTS];
+};
 
-template <int K, int L, int NOBJ>
-__global__ __launch_bounds__(256) void volume_render_compose_kernel(
-    ComposeRaws raws, int n_objects, const float* __restrict__ z, const float* __restrict__ rd, int64_t n_rays,
+// HOST scales into the kernel argument; false for one that is NaN, infinite or <= 0.
+inline bool read_scales(const float* scales, int n_objects, ComposeScales& sc) {
+  for (int k = 0; k < n_objects; ++k) {
+    const float v = scales[k];
+    if (!(v - v == 0.0f && v > 0.0f)) return false;
+    sc.s[k] = v;
+  }
+  return true;
+}
+
+template <bool SCALED>
+__device__ __forceinline__ float object_sigma(float xs, float scale) {
+  if constexpr (SCALED) return __fdiv_rn(raw_sigma(xs), scale);
+  else return raw_sigma(xs);
+}
+
+// SCALED instances ask for two waves per SIMD (<= 256 registers): the divisions' temporaries would otherwise take
+// the <8, 64, 8> instance past it.  The unscaled instances keep the default bound and their code.
+template <int K, int L, int NOBJ, bool SCALED>
+__global__ __launch_bounds__(256, SCALED ? 2 : 1) void volume_render_compose_kernel(
+    ComposeRaws raws, ComposeScales scales, int n_objects, const float* __restrict__ z, const float* __restrict__ rd,
+    int64_t n_rays,
     int S_in, float* __restrict__ rgb, float* __restrict__ disp, float* __restrict__ acc,
     float* __restrict__ weights, float* __restrict__ depth, float* __restrict__ acc_objects) {
   static_assert(K <= kMaxRun && (L == 16 || L == 64) && NOBJ >= 1 && NOBJ <= CN_MAX_SCENE_OBJECTS, "instance");
@@ -478,7 +502,7 @@ __global__ __launch_bounds__(256) void volume_render_compose_kernel(
 #pragma unroll
     for (int i = 0; i < K; ++i) {
       if (i < run && j0 + i < S) {
-        const float s = raw_sigma(rv[i].w);
+        const float s = object_sigma<SCALED>(rv[i].w, scales.s[k]);
         sk[k][i] = s;
         sig[i] = __fadd_rn(sig[i], s);
         if (s != 0.0f) {  // active (a NaN density is)
@@ -563,14 +587,14 @@ __global__ __launch_bounds__(256) void volume_render_compose_kernel(
   }
 }
 
-template <int NOBJ>
-void launch_compose(const ComposeRaws& raws, int n_objects, const float* z, const float* rd, int64_t n_rays, int S,
-                    float* rgb, float* disp, float* acc, float* weights, float* depth, float* acc_objects,
-                    hipStream_t stream) {
+template <int NOBJ, bool SCALED>
+void launch_compose(const ComposeRaws& raws, const ComposeScales& scales, int n_objects, const float* z, const float* rd,
+                    int64_t n_rays, int S, float* rgb, float* disp, float* acc, float* weights, float* depth,
+                    float* acc_objects, hipStream_t stream) {
   const dim3 g16(static_cast<unsigned>(cn::ceil_div(n_rays, 16))), g64(static_cast<unsigned>(cn::ceil_div(n_rays, 4)));
 #define CN_COMPOSE_LAUNCH(K, L, GRID)                                                                         \
-  hipLaunchKernelGGL((volume_render_compose_kernel<K, L, NOBJ>), GRID, dim3(256), 0, stream, raws, n_objects, z, rd, \
-                     n_rays, S, rgb, disp, acc, weights, depth, acc_objects)
+  hipLaunchKernelGGL((volume_render_compose_kernel<K, L, NOBJ, SCALED>), GRID, dim3(256), 0, stream, raws, scales, \
+                     n_objects, z, rd, n_rays, S, rgb, disp, acc, weights, depth, acc_objects)
   if (S <= 64) CN_COMPOSE_LAUNCH(4, 16, g16);
   else if (S <= 128) CN_COMPOSE_LAUNCH(8, 16, g16);
   else if (S <= 256) CN_COMPOSE_LAUNCH(4, 64, g64);
@@ -578,28 +602,52 @@ void launch_compose(const ComposeRaws& raws, int n_objects, const float* z, cons
 #undef CN_COMPOSE_LAUNCH
 }
 
+// The two entries' body: scales NULL is the unscaled entry.
+int compose_entry(const float* const* raws, const float* scales, bool scaled, int n_objects, const float* z,
+                  const float* rd, int64_t n_rays, int64_t n_samples, float* rgb, float* disp, float* acc,
+                  float* weights, float* depth, float* acc_objects, cn_stream_t stream) {
+  CN_CHECK_ARG(raws && z && rd && rgb && disp && acc && depth && (scales || !scaled));
+  CN_CHECK_ARG(n_objects >= 1 && n_objects <= CN_MAX_SCENE_OBJECTS);
+  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && n_samples <= kMaxSamples);
+  CN_CHECK_ARG(cn::aligned16(z) && cn::aligned16(weights));
+  ComposeRaws p = {};
+  ComposeScales sc = {};
+  for (int k = 0; k < n_objects; ++k) {
+    CN_CHECK_ARG(raws[k] && cn::aligned16(raws[k]));
+    p.p[k] = raws[k];
+  }
+  if (scaled) CN_CHECK_ARG(read_scales(scales, n_objects, sc));
+  const int s = static_cast<int>(n_samples);
+  hipStream_t st = cn::as_stream(stream);
+#define CN_COMPOSE(NOBJ)                                                                                              \
+  do {                                                                                                                \
+    if (scaled) launch_compose<NOBJ, true>(p, sc, n_objects, z, rd, n_rays, s, rgb, disp, acc, weights, depth, acc_objects, st); \
+    else launch_compose<NOBJ, false>(p, sc, n_objects, z, rd, n_rays, s, rgb, disp, acc, weights, depth, acc_objects, st);       \
+  } while (0)
+  // the object count's compile-time bound: 1, 2, 4 or 8
+  if (n_objects == 1) CN_COMPOSE(1);
+  else if (n_objects == 2) CN_COMPOSE(2);
+  else if (n_objects <= 4) CN_COMPOSE(4);
+  else CN_COMPOSE(8);
+#undef CN_COMPOSE
+  return cn::launch_status();
+}
+
 }  // namespace
 
 extern "C" int cn_volume_render_compose(const float* const* raws, int n_objects, const float* z, const float* rd,
                                         int64_t n_rays, int64_t n_samples, float* rgb, float* disp, float* acc,
                                         float* weights, float* depth, float* acc_objects, cn_stream_t stream) {
-  CN_CHECK_ARG(raws && z && rd && rgb && disp && acc && depth);
-  CN_CHECK_ARG(n_objects >= 1 && n_objects <= CN_MAX_SCENE_OBJECTS);
-  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && n_samples <= kMaxSamples);
-  CN_CHECK_ARG(cn::aligned16(z) && cn::aligned16(weights));
-  ComposeRaws p = {};
-  for (int k = 0; k < n_objects; ++k) {
-    CN_CHECK_ARG(raws[k] && cn::aligned16(raws[k]));
-    p.p[k] = raws[k];
-  }
-  const int s = static_cast<int>(n_samples);
-  hipStream_t st = cn::as_stream(stream);
-  // the object count's compile-time bound: 1, 2, 4 or 8
-  if (n_objects == 1) launch_compose<1>(p, n_objects, z, rd, n_rays, s, rgb, disp, acc, weights, depth, acc_objects, st);
-  else if (n_objects == 2) launch_compose<2>(p, n_objects, z, rd, n_rays, s, rgb, disp, acc, weights, depth, acc_objects, st);
-  else if (n_objects <= 4) launch_compose<4>(p, n_objects, z, rd, n_rays, s, rgb, disp, acc, weights, depth, acc_objects, st);
-  else launch_compose<8>(p, n_objects, z, rd, n_rays, s, rgb, disp, acc, weights, depth, acc_objects, st);
-  return cn::launch_status();
+  return compose_entry(raws, nullptr, false, n_objects, z, rd, n_rays, n_samples, rgb, disp, acc, weights, depth,
+                       acc_objects, stream);
+}
+
+extern "C" int cn_volume_render_compose_scaled(const float* const* raws, const float* scales, int n_objects,
+                                               const float* z, const float* rd, int64_t n_rays, int64_t n_samples,
+                                               float* rgb, float* disp, float* acc, float* weights, float* depth,
+                                               float* acc_objects, cn_stream_t stream) {
+  return compose_entry(raws, scales, true, n_objects, z, rd, n_rays, n_samples, rgb, disp, acc, weights, depth,
+                       acc_objects, stream);
 }
 
 // ---------------------------------------------------------------- backward
@@ -837,12 +885,17 @@ struct ComposeGrads {
   float* p[CN_MAX_SCENE_OBJECTS];
 };
 
-template <int K, int L, int NOBJ>
+// SCALED (cn_volume_render_compose_scaled_backward): the density is softplus20(xs - 1) / s_k, the density's
+// gradient goes back through that division, and with scale_partials every wave leaves, per object, its sum of
+// -d sigma_k sigma_k / s_k at scale_partials[k * n_waves + wave] (n_waves = the waves that hold a ray): lanes in
+// the row tree's order, the rows ascending, no atomics.
+template <int K, int L, int NOBJ, bool SCALED>
 __global__ __launch_bounds__(256) void volume_render_compose_backward_kernel(
-    ComposeRaws raws, int n_objects, const float* __restrict__ z, const float* __restrict__ rd, int64_t n_rays,
-    int S_in, const float* __restrict__ g_rgb, const float* __restrict__ g_disp, const float* __restrict__ g_acc,
-    const float* __restrict__ g_w, const float* __restrict__ g_depth, const float* __restrict__ g_ao,
-    ComposeGrads d_raws, float* __restrict__ d_rd, int accumulate_rd) {
+    ComposeRaws raws, ComposeScales scales, int n_objects, const float* __restrict__ z, const float* __restrict__ rd,
+    int64_t n_rays, int S_in, const float* __restrict__ g_rgb, const float* __restrict__ g_disp,
+    const float* __restrict__ g_acc, const float* __restrict__ g_w, const float* __restrict__ g_depth,
+    const float* __restrict__ g_ao, ComposeGrads d_raws, float* __restrict__ d_rd, int accumulate_rd,
+    float* __restrict__ scale_partials) {
   static_assert(K <= kMaxRun && (L == 16 || L == 64) && NOBJ >= 1 && NOBJ <= CN_MAX_SCENE_OBJECTS, "instance");
   __shared__ float4 slds[4 * 80 * K];  // per wave: one object's rows in, then its d raw rows out
   const int sub = threadIdx.x & (L - 1), lane = threadIdx.x & 63;
@@ -893,7 +946,7 @@ __global__ __launch_bounds__(256) void volume_render_compose_backward_kernel(
 #pragma unroll
     for (int i = 0; i < K; ++i) {
       if (i < run && j0 + i < S) {
-        const float s = raw_sigma(rv[i].w);
+        const float s = object_sigma<SCALED>(rv[i].w, scales.s[k]);
         sig[i] = __fadd_rn(sig[i], s);
         if (s != 0.0f) {  // active (a NaN density is)
           const float c0 = raw_colour(rv[i].x), c1 = raw_colour(rv[i].y), c2 = raw_colour(rv[i].z);
@@ -950,6 +1003,7 @@ __global__ __launch_bounds__(256) void volume_render_compose_backward_kernel(
     __builtin_amdgcn_wave_barrier();  // the previous object's copy-out reads stay ahead of these stores
     stage_rows_in<K>(reinterpret_cast<const float4*>(raws.p[k]) + rw0 * S_in, nq, sl, lane);
     __builtin_amdgcn_wave_barrier();
+    float dscale = 0.0f;  // SCALED: this lane's part of d_scales[k]
     if (live) {
       float4 rv[K];
       load_raw_lds<K>(sl, q0, j0, run, S_in, rv);
@@ -958,7 +1012,7 @@ __global__ __launch_bounds__(256) void volume_render_compose_backward_kernel(
         const int j = j0 + i;
         if (!(i < run && j < S_in)) continue;
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);  // an inactive object's row, and the sample-free S_in == 1
-        const float s = j < S ? raw_sigma(rv[i].w) : 0.0f;
+        const float s = j < S ? object_sigma<SCALED>(rv[i].w, scales.s[k]) : 0.0f;
         if (s != 0.0f) {
           const float s0 = cn::sigmoid_hw(rv[i].x), s1 = cn::sigmoid_hw(rv[i].y), s2 = cn::sigmoid_hw(rv[i].z);
           if (cnt[i] > 1) {
@@ -970,36 +1024,116 @@ __global__ __launch_bounds__(256) void volume_render_compose_backward_kernel(
             // through the mixed colour and the shares: w (g_rgb . (c_k - c) + g_ao[k] - sum_j g_ao[j] share_j) / sigma
             float mixg = g.r0 * (c0 - lone[i][0]) + g.r1 * (c1 - lone[i][1]) + g.r2 * (c2 - lone[i][2]);
             if (g_ao) mixg += gao[k] - alone[i];
-            o.w = (dsd[i] * (dist[i] * nrm) + w[i] * mixg / sig[i]) * sigma_slope(rv[i].w);
+            const float dsig = dsd[i] * (dist[i] * nrm) + w[i] * mixg / sig[i];
+            o.w = dsig * sigma_slope(rv[i].w);
+            if constexpr (SCALED) dscale -= dsig * s / scales.s[k];
           } else {  // the only active object: the plain backward's row
             o.x = colour_grad(w[i], g.r0, s0);
             o.y = colour_grad(w[i], g.r1, s1);
             o.z = colour_grad(w[i], g.r2, s2);
-            o.w = dsd[i] * (dist[i] * nrm) * sigma_slope(rv[i].w);
+            const float dsig = dsd[i] * (dist[i] * nrm);
+            o.w = dsig * sigma_slope(rv[i].w);
+            if constexpr (SCALED) dscale -= dsig * s / scales.s[k];
           }
+          if constexpr (SCALED) o.w = o.w / scales.s[k];
         }
         sl[pad4(q0 + i)] = o;
       }
     }
     __builtin_amdgcn_wave_barrier();  // the copy-out reads quads other lanes wrote
     stage_rows_out<K>(reinterpret_cast<float4*>(d_raws.p[k]) + rw0 * S_in, nq, sl, lane);
+    if constexpr (SCALED) {
+      if (scale_partials) {  // uniform; every lane of the wave is here (a ray past n_rays holds 0)
+        const float t = ray_sum<64>(dscale);
+        const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+        const int64_t n_waves = (n_rays + (64 / L - 1)) / (64 / L);
+        if (lane == 63) scale_partials[k * n_waves + wave] = t;
+      }
+    }
   }
 }
 
-template <int NOBJ>
-void launch_compose_backward(const ComposeRaws& raws, int n_objects, const float* z, const float* rd, int64_t n_rays,
-                             int S, const float* g_rgb, const float* g_disp, const float* g_acc, const float* g_w,
-                             const float* g_depth, const float* g_ao, const ComposeGrads& d_raws, float* d_rd,
-                             int accumulate_rd, hipStream_t stream) {
+// d_scales[k] from the waves' partials, one block per object: lane t sums partials t, t + 256, ... in ascending
+// order, then a fixed tree over the block's lanes.
+__global__ __launch_bounds__(256) void compose_scales_reduce_kernel(const float* __restrict__ partials, int64_t n_waves,
+                                                                    float* __restrict__ d_scales) {
+  __shared__ float red[256];
+  const int k = blockIdx.x;
+  float acc = 0.0f;
+  for (int64_t b = threadIdx.x; b < n_waves; b += 256) acc += partials[k * n_waves + b];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) d_scales[k] = red[0];
+}
+
+// The waves that hold a ray: cn_volume_render_compose_scaled_backward's partials per object.
+inline int64_t compose_waves(int64_t n_rays, int64_t n_samples) {
+  return cn::ceil_div(n_rays, (int64_t)(n_samples <= 128 ? 4 : 1));
+}
+
+template <int NOBJ, bool SCALED>
+void launch_compose_backward(const ComposeRaws& raws, const ComposeScales& scales, int n_objects, const float* z,
+                             const float* rd, int64_t n_rays, int S, const float* g_rgb, const float* g_disp,
+                             const float* g_acc, const float* g_w, const float* g_depth, const float* g_ao,
+                             const ComposeGrads& d_raws, float* d_rd, int accumulate_rd, float* scale_partials,
+                             hipStream_t stream) {
   const dim3 g16(static_cast<unsigned>(cn::ceil_div(n_rays, 16))), g64(static_cast<unsigned>(cn::ceil_div(n_rays, 4)));
 #define CN_COMPOSE_BWD_LAUNCH(K, L, GRID)                                                                            \
-  hipLaunchKernelGGL((volume_render_compose_backward_kernel<K, L, NOBJ>), GRID, dim3(256), 0, stream, raws, n_objects, \
-                     z, rd, n_rays, S, g_rgb, g_disp, g_acc, g_w, g_depth, g_ao, d_raws, d_rd, accumulate_rd)
+  hipLaunchKernelGGL((volume_render_compose_backward_kernel<K, L, NOBJ, SCALED>), GRID, dim3(256), 0, stream, raws,   \
+                     scales, n_objects, z, rd, n_rays, S, g_rgb, g_disp, g_acc, g_w, g_depth, g_ao, d_raws, d_rd,      \
+                     accumulate_rd, scale_partials)
   if (S <= 64) CN_COMPOSE_BWD_LAUNCH(4, 16, g16);
   else if (S <= 128) CN_COMPOSE_BWD_LAUNCH(8, 16, g16);
   else if (S <= 256) CN_COMPOSE_BWD_LAUNCH(4, 64, g64);
   else CN_COMPOSE_BWD_LAUNCH(8, 64, g64);
 #undef CN_COMPOSE_BWD_LAUNCH
+}
+
+// The two entries' body: scaled false is the unscaled entry (no scales, d_scales or workspace).
+int compose_backward_entry(const float* const* raws, const float* scales, bool scaled, int n_objects, const float* z,
+                           const float* rd, int64_t n_rays, int64_t n_samples, const float* g_rgb, const float* g_disp,
+                           const float* g_acc, const float* g_weights, const float* g_depth, const float* g_acc_objects,
+                           float* const* d_raws, float* d_rd, int accumulate_rd, float* d_scales, float* workspace,
+                           cn_stream_t stream) {
+  CN_CHECK_ARG(raws && d_raws && z && rd && (accumulate_rd == 0 || accumulate_rd == 1) && (scales || !scaled));
+  CN_CHECK_ARG(n_objects >= 1 && n_objects <= CN_MAX_SCENE_OBJECTS);
+  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && n_samples <= kMaxSamples);
+  CN_CHECK_ARG(cn::aligned16(z) && (!d_scales || workspace));
+  ComposeRaws p = {};
+  ComposeGrads d = {};
+  ComposeScales sc = {};
+  for (int k = 0; k < n_objects; ++k) {
+    CN_CHECK_ARG(raws[k] && cn::aligned16(raws[k]) && d_raws[k] && cn::aligned16(d_raws[k]));
+    p.p[k] = raws[k];
+    d.p[k] = d_raws[k];
+  }
+  if (scaled) CN_CHECK_ARG(read_scales(scales, n_objects, sc));
+  const int s = static_cast<int>(n_samples);
+  hipStream_t st = cn::as_stream(stream);
+  float* partials = d_scales ? workspace : nullptr;
+#define CN_COMPOSE_BWD(NOBJ)                                                                                          \
+  do {                                                                                                                \
+    if (scaled)                                                                                                       \
+      launch_compose_backward<NOBJ, true>(p, sc, n_objects, z, rd, n_rays, s, g_rgb, g_disp, g_acc, g_weights, g_depth, \
+                                          g_acc_objects, d, d_rd, accumulate_rd, partials, st);                       \
+    else                                                                                                              \
+      launch_compose_backward<NOBJ, false>(p, sc, n_objects, z, rd, n_rays, s, g_rgb, g_disp, g_acc, g_weights, g_depth, \
+                                           g_acc_objects, d, d_rd, accumulate_rd, nullptr, st);                       \
+  } while (0)
+  // the object count's compile-time bound, as the forward
+  if (n_objects == 1) CN_COMPOSE_BWD(1);
+  else if (n_objects == 2) CN_COMPOSE_BWD(2);
+  else if (n_objects <= 4) CN_COMPOSE_BWD(4);
+  else CN_COMPOSE_BWD(8);
+#undef CN_COMPOSE_BWD
+  if (partials)
+    hipLaunchKernelGGL(compose_scales_reduce_kernel, dim3(n_objects), dim3(256), 0, st, partials,
+                       compose_waves(n_rays, n_samples), d_scales);
+  return cn::launch_status();
 }
 
 }  // namespace
@@ -1010,27 +1144,25 @@ extern "C" int cn_volume_render_compose_backward(const float* const* raws, int n
                                                  const float* g_weights, const float* g_depth,
                                                  const float* g_acc_objects, float* const* d_raws, float* d_rd,
                                                  int accumulate_rd, cn_stream_t stream) {
-  CN_CHECK_ARG(raws && d_raws && z && rd && (accumulate_rd == 0 || accumulate_rd == 1));
-  CN_CHECK_ARG(n_objects >= 1 && n_objects <= CN_MAX_SCENE_OBJECTS);
-  CN_CHECK_ARG(n_rays > 0 && n_samples > 0 && n_samples <= kMaxSamples);
-  CN_CHECK_ARG(cn::aligned16(z));
-  ComposeRaws p = {};
-  ComposeGrads d = {};
-  for (int k = 0; k < n_objects; ++k) {
-    CN_CHECK_ARG(raws[k] && cn::aligned16(raws[k]) && d_raws[k] && cn::aligned16(d_raws[k]));
-    p.p[k] = raws[k];
-    d.p[k] = d_raws[k];
-  }
-  const int s = static_cast<int>(n_samples);
-  hipStream_t st = cn::as_stream(stream);
-#define CN_COMPOSE_BWD(NOBJ)                                                                                          \
-  launch_compose_backward<NOBJ>(p, n_objects, z, rd, n_rays, s, g_rgb, g_disp, g_acc, g_weights, g_depth, g_acc_objects, \
-                                d, d_rd, accumulate_rd, st)
-  // the object count's compile-time bound, as the forward
-  if (n_objects == 1) CN_COMPOSE_BWD(1);
-  else if (n_objects == 2) CN_COMPOSE_BWD(2);
-  else if (n_objects <= 4) CN_COMPOSE_BWD(4);
-  else CN_COMPOSE_BWD(8);
-#undef CN_COMPOSE_BWD
-  return cn::launch_status();
+  return compose_backward_entry(raws, nullptr, false, n_objects, z, rd, n_rays, n_samples, g_rgb, g_disp, g_acc,
+                                g_weights, g_depth, g_acc_objects, d_raws, d_rd, accumulate_rd, nullptr, nullptr, stream);
+}
+
+extern "C" int64_t cn_volume_render_compose_scaled_backward_workspace_floats(int64_t n_rays, int64_t n_samples,
+                                                                             int n_objects) {
+  if (n_rays <= 0 || n_samples <= 0 || n_samples > kMaxSamples || n_objects < 1 || n_objects > CN_MAX_SCENE_OBJECTS)
+    return -1;
+  return compose_waves(n_rays, n_samples) * n_objects;
+}
+
+extern "C" int cn_volume_render_compose_scaled_backward(const float* const* raws, const float* scales, int n_objects,
+                                                        const float* z, const float* rd, int64_t n_rays,
+                                                        int64_t n_samples, const float* g_rgb, const float* g_disp,
+                                                        const float* g_acc, const float* g_weights,
+                                                        const float* g_depth, const float* g_acc_objects,
+                                                        float* const* d_raws, float* d_rd, int accumulate_rd,
+                                                        float* d_scales, float* workspace, cn_stream_t stream) {
+  return compose_backward_entry(raws, scales, true, n_objects, z, rd, n_rays, n_samples, g_rgb, g_disp, g_acc,
+                                g_weights, g_depth, g_acc_objects, d_raws, d_rd, accumulate_rd, d_scales, workspace,
+                                stream);
 }

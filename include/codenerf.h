@@ -605,6 +605,31 @@ int cn_volume_render_compose(const float* const* raws, int n_objects, const floa
 int cn_object_rays(const float* ro, const float* rd, int64_t n_rays, const float* poses, int n_objects,
                    float* ro_out, float* rd_out, cn_stream_t stream);
 
+/* --- Scene composition with uniform scale: similarity poses --------------
+ * A similarity pose is 13 floats: R row-major (object to world), t, and the scale s, finite and > 0: how many
+ * times larger than its canonical size the object appears.  A medium enlarged by s has extinction
+ * sigma(x / s) / s, so the opacity along a chord through the object does not depend on its size; and dividing
+ * the object-frame ray by s keeps the ray parameter, so one set of depths still serves every object.
+ *   Object rays: u = cn_object_rays' result for (R, t), then ro_out[i] = u[i] / s, an IEEE division, rounded;
+ *     rd_out the same from rd.  ro_out + z rd_out is the world point ro + z rd in the object's canonical frame.
+ *   Composition: sigma_k = softplus20(xs - 1) / s_k, the division rounded in fp32; everything after that is the
+ *     rule above on these sigma_k (active iff sigma_k != 0, the ascending sum, the three-case colour and share,
+ *     cn_volume_render's integral with the world rd).  A culled slot stays exactly inactive (0 / s = 0).
+ * With every s = 1 the scaled entries return the unscaled entries' bits.  The field kernels, the culls and the
+ * samplers see object-frame rays and raw rows only, and are unchanged. */
+
+/* cn_object_rays with HOST poses of n_objects x 13 floats (R, t, s).  One launch, no workspace.
+ * CN_EINVAL: what cn_object_rays refuses; a scale that is NaN, infinite or <= 0. */
+int cn_object_rays_scaled(const float* ro, const float* rd, int64_t n_rays, const float* poses, int n_objects,
+                          float* ro_out, float* rd_out, cn_stream_t stream);
+
+/* cn_volume_render_compose with the objects' scales: a HOST array scales[n_objects].  One launch, no workspace.
+ * CN_EINVAL: what cn_volume_render_compose refuses; scales NULL; a scale that is NaN, infinite or <= 0. */
+int cn_volume_render_compose_scaled(const float* const* raws, const float* scales, int n_objects, const float* z,
+                                    const float* rd, int64_t n_rays, int64_t n_samples, float* rgb, float* disp,
+                                    float* acc, float* weights, float* depth, float* acc_objects,
+                                    cn_stream_t stream);
+
 /* --- Iso-surface extraction (inference) ---------------------------------
  * A node grid to a triangle mesh, on the device: marching tetrahedra on the Kuhn (Freudenthal) split
  * of each cell.  The split is the same in every cell, so neighbouring cells agree on every shared
@@ -1032,6 +1057,47 @@ int64_t cn_object_rays_backward_workspace_floats(int64_t n_rays, int n_objects);
 int cn_object_rays_backward(const float* g_ro_obj, const float* g_rd_obj, const float* ro, const float* rd,
                             int64_t n_rays, const float* poses, int n_objects, float* d_ro, float* d_rd,
                             int accumulate, float* d_poses, float* workspace, cn_stream_t stream);
+
+/* --- Scene composition with uniform scale, backward ----------------------
+ * The two backwards above for similarity poses (the rule is beside cn_object_rays_scaled).  Stream-ordered, no
+ * synchronisation, no float atomics, no state; every element of every output is written. */
+
+/* Floats of cn_volume_render_compose_scaled_backward's workspace (its waves' partial scale sums), or -1 for
+ * sizes it refuses. */
+int64_t cn_volume_render_compose_scaled_backward_workspace_floats(int64_t n_rays, int64_t n_samples, int n_objects);
+
+/* Backward of cn_volume_render_compose_scaled: cn_volume_render_compose_backward's derivative with sigma_k read
+ * as the scaled density softplus20(xs - 1) / s_k.  With d sigma_k as defined there:
+ *   d raw_k[3] = d sigma_k softplus20'(xs - 1) / s_k (the product, then the division);
+ *   d_scales[k] = - sum_r sum_s d sigma_k[r][s] sigma_k[r][s] / s_k; an inactive slot contributes exactly 0.
+ * d_scales: device, n_objects floats, written; may be NULL, and then no workspace is needed.  Its sums run in a
+ * fixed order (a wave's lanes, then the waves' partials in `workspace`, one block per object): two runs give
+ * the same bits.  One launch, two with d_scales.  With every scale 1 and d_scales NULL the outputs are
+ * cn_volume_render_compose_backward's bits.
+ * CN_EINVAL: what cn_volume_render_compose_backward refuses; scales NULL; a scale that is NaN, infinite or
+ * <= 0; d_scales without a workspace. */
+int cn_volume_render_compose_scaled_backward(const float* const* raws, const float* scales, int n_objects,
+                                             const float* z, const float* rd, int64_t n_rays, int64_t n_samples,
+                                             const float* g_rgb, const float* g_disp, const float* g_acc,
+                                             const float* g_weights, const float* g_depth,
+                                             const float* g_acc_objects, float* const* d_raws, float* d_rd,
+                                             int accumulate_rd, float* d_scales, float* workspace,
+                                             cn_stream_t stream);
+
+/* Floats of cn_object_rays_scaled_backward's workspace, or -1 for sizes it refuses. */
+int64_t cn_object_rays_scaled_backward_workspace_floats(int64_t n_rays, int n_objects);
+
+/* Backward of cn_object_rays_scaled: cn_object_rays_backward with HOST poses of n_objects x 13 floats and
+ * d_poses (device) n_objects x 13: dR, dt, ds.  With g' = g / s_k (g_ro_obj and g_rd_obj, the division rounded):
+ *   d_ro, d_rd, dR_k, dt_k: cn_object_rays_backward's formulas on g';
+ *   ds_k = - sum_r sum_i (ro_out[k][r][i] g_ro_obj[k][r][i] + rd_out[k][r][i] g_rd_obj[k][r][i]) / s_k, with
+ *     ro_out, rd_out the forward's values, formed again;
+ * the 13 sums per object reduced in cn_object_rays_backward's fixed order.  With every scale 1 the first 12
+ * columns, d_ro and d_rd are cn_object_rays_backward's bits.
+ * CN_EINVAL: what cn_object_rays_backward refuses; a scale that is NaN, infinite or <= 0. */
+int cn_object_rays_scaled_backward(const float* g_ro_obj, const float* g_rd_obj, const float* ro, const float* rd,
+                                   int64_t n_rays, const float* poses, int n_objects, float* d_ro, float* d_rd,
+                                   int accumulate, float* d_poses, float* workspace, cn_stream_t stream);
 
 /* Backward of cn_occupancy_expand: g_compact (M', 4) row j = g_raw (n_rays, n_samples, 4) row
  * sample_index[j]; the gradients of culled slots are dropped (the empty row is a constant).  workspace: what
