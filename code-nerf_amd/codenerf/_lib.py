@@ -20,13 +20,16 @@ CN_OK, CN_EINVAL, CN_EUNSUPPORTED = 0, -1, -2
 CN_NUM_PARAMS = 18
 CN_FMT_F32, CN_FMT_BF16X3, CN_FMT_BF16X3_T, CN_FMT_F32_W16, CN_FMT_F32_W16_T, CN_FMT_BF16X3_W16 = 0, 1, 2, 3, 4, 5
 CN_FMT_F32_W16_FOLD = 6
+CN_FMT_F16 = 7
 FORMATS = {"f32": CN_FMT_F32, "bf16x3": CN_FMT_BF16X3, "bf16x3_t": CN_FMT_BF16X3_T, "f32_w16": CN_FMT_F32_W16,
-           "f32_w16_t": CN_FMT_F32_W16_T, "bf16x3_w16": CN_FMT_BF16X3_W16, "f32_w16_fold": CN_FMT_F32_W16_FOLD}
+           "f32_w16_t": CN_FMT_F32_W16_T, "bf16x3_w16": CN_FMT_BF16X3_W16, "f32_w16_fold": CN_FMT_F32_W16_FOLD,
+           "f16": CN_FMT_F16}
 
 
 def kernel_format(precision: str) -> str:
     """Packed format / field kernel that runs a precision: "f32" -> the 16x16x4 two-waves-per-SIMD
-    fp32 kernel ("f32_w16"; CODENERF_F32_KERNEL=v1 selects the 32x32x2 one), "bf16x3" -> itself."""
+    fp32 kernel ("f32_w16"; CODENERF_F32_KERNEL=v1 selects the 32x32x2 one), "bf16x3" and "f16" (the
+    one-product fp16 inference kernel, mlp_f16.hip) -> themselves."""
     if precision == "f32":
         return "f32" if os.environ.get("CODENERF_F32_KERNEL") == "v1" else "f32_w16"
     if precision == "f32_v1":          # fp32, the 32x32x2 one-wave-per-SIMD kernel (mlp.hip)

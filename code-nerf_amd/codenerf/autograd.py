@@ -989,12 +989,24 @@ def _code_rows(z_s, z_t):
     return z_s, z_t
 
 
+def _require_backward(model):
+    """The fp16 field kernel (precision "f16") is inference only: a call that needs gradients through such a
+    model is refused instead of running in another arithmetic."""
+    if getattr(model, "precision", "f32") == "f16":
+        raise NotImplementedError(
+            "precision 'f16' is inference only (the fp16 field kernel has no backward): run the call under "
+            "torch.no_grad() with detached inputs and frozen weights, or set the model's precision to 'f32' or "
+            "'bf16x3' for a call that needs gradients")
+
+
 def mlp_forward_autograd(model, z_s, z_t, x):
+    _require_backward(model)
     cs, ct = _code_rows(z_s, z_t)
     return MLPForward.apply(getattr(model, "train_precision", "f32"), x, cs, ct, *model.param_list())
 
 
 def _field_meta(model, cs, ct, n_samples, chunk_rows, fx, fd, code_index, rd=None, ro=None, pair=None):
+    _require_backward(model)
     sink = getattr(cs, "_cn_sink", None)
     return _FieldMeta(n_samples, chunk_rows, fx, fd, code_index=code_index,
                       precision=getattr(model, "precision", "f32"),

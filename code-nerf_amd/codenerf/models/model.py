@@ -66,7 +66,9 @@ class CodeNeRFModel(torch.nn.Module):
         self.fc_rgb = torch.nn.Linear(h + texture_code_size, 3)
         # field-kernel arithmetic: "f32" (exact-product fp32 MFMA, the reference's precision;
         # default) or "bf16x3" (opt-in: 3-product bf16 split, fp32 accumulate, ~2^-17 relative
-        # per product; parity-tested at the same tolerances incl. trained-magnitude weights)
+        # per product; parity-tested at the same tolerances incl. trained-magnitude weights) or "f16"
+        # (opt-in, inference only: one fp16 product per GEMM, fp32 accumulate -- several times faster,
+        # not the reference's bits; a call that needs gradients raises NotImplementedError)
         self.precision = os.environ.get("CODENERF_PRECISION", "f32")
         # arithmetic of the training backward's weight-gradient / dX GEMMs, independent of the
         # inference format: the reference trains fully in fp32

@@ -471,7 +471,8 @@ def mlp_pack(params: Sequence[Tensor], precision: str = "f32") -> Tensor:
     fragments for the 3-product split on v_mfma_f32_32x32x16_bf16 (include/codenerf.h);
     "bf16x3_t": the transposed 3xbf16 pack of the fused backward; "f32_w16_fold": the "f32_w16"
     pack with fc_out's feature rows folded into layer_dir1 (frozen-weight inference; read by
-    mlp_forward / radiance_field together with fold_bias rows).
+    mlp_forward / radiance_field together with fold_bias rows); "f16": fp16 fragments (weights rounded
+    to nearest even) for the one-product inference kernel on v_mfma_f32_32x32x16_f16.
     """
     lib = _lib_ready()
     assert len(params) == _lib.CN_NUM_PARAMS, "expected the 18 CodeNeRFModel weight/bias tensors"

@@ -1,6 +1,6 @@
 // The field's C entry points (include/codenerf.h): argument checks, kernel arguments, the launch.
 // No kernel lives here -- the kernels and their launchers are mlp.hip (fp32 32x32x2), mlp_f32.hip
-// (fp32 16x16x4), mlp_x3.hip and mlp_x3w.hip (3xbf16).
+// (fp32 16x16x4), mlp_x3.hip and mlp_x3w.hip (3xbf16), mlp_f16.hip (fp16, inference only).
 //
 // Every entry that takes a field call's geometry, codes and frequency tables gets their checks and its
 // FieldArgs from field_args (encoded rows: encoded_args) and states only what is its own: its buffers,
@@ -99,7 +99,8 @@ int make_params(const float* const* params, Params* P) {
 }
 
 bool valid_fmt(int fmt) {
-  return fmt == CN_FMT_F32 || fmt == CN_FMT_BF16X3 || fmt == CN_FMT_F32_W16 || fmt == CN_FMT_BF16X3_W16;
+  return fmt == CN_FMT_F32 || fmt == CN_FMT_BF16X3 || fmt == CN_FMT_F32_W16 || fmt == CN_FMT_BF16X3_W16 ||
+         fmt == CN_FMT_F16;
 }
 bool valid_pack_fmt(int fmt) {
   return valid_fmt(fmt) || fmt == CN_FMT_BF16X3_T || fmt == CN_FMT_F32_W16_T || fmt == CN_FMT_F32_W16_FOLD;
@@ -117,6 +118,7 @@ int launch_field(int fmt, int mode, FieldArgs& a, hipStream_t st) {
   if (fmt == CN_FMT_F32_W16) return launch_field_w16(mode, a, st);
   if (fmt == CN_FMT_BF16X3_W16) return launch_field_x3w(mode, a, st);
   if (fmt == CN_FMT_F32_W16_FOLD) return launch_field_w16_fold(mode, a, st);
+  if (fmt == CN_FMT_F16) return launch_field_f16(mode, a, st);
   return launch_field_v1(mode, a, st);
 }
 
@@ -198,6 +200,7 @@ extern "C" int64_t cn_mlp_packed_floats(int fmt) {
   if (fmt == CN_FMT_F32_W16 || fmt == CN_FMT_F32_W16_T) return packed_floats_w16();
   if (fmt == CN_FMT_F32_W16_FOLD) return packed_floats_w16_fold();
   if (fmt == CN_FMT_BF16X3_W16) return packed_floats_x3w();
+  if (fmt == CN_FMT_F16) return packed_floats_f16();
   return fmt == CN_FMT_F32 ? kPackedFloats : packed_floats_x3();
 }
 
@@ -210,6 +213,7 @@ extern "C" int cn_mlp_pack(const float* const* params, int fmt, float* packed, c
   if (fmt == CN_FMT_F32_W16_T) return launch_pack_w16t(P, packed, cn::as_stream(stream));
   if (fmt == CN_FMT_F32_W16_FOLD) return launch_pack_w16_fold(P, packed, cn::as_stream(stream));
   if (fmt == CN_FMT_BF16X3_W16) return launch_pack_x3w(P, packed, cn::as_stream(stream));
+  if (fmt == CN_FMT_F16) return launch_pack_f16(P, packed, cn::as_stream(stream));
   return launch_pack_v1(P, packed, cn::as_stream(stream));
 }
 

@@ -386,6 +386,11 @@ int64_t packed_floats_x3w();
 int launch_pack_x3w(const Params& P, float* packed, hipStream_t st);
 int launch_field_x3w(int mode, FieldArgs& a, hipStream_t st);
 
+// fp16 one-product variant (mlp_f16.hip): inference forward only (no masks, no planes).
+int64_t packed_floats_f16();
+int launch_pack_f16(const Params& P, float* packed, hipStream_t st);
+int launch_field_f16(int mode, FieldArgs& a, hipStream_t st);
+
 // Pre-encoded rows: the same 2P+2 values gathered from x (base = column offset).
 template <int P, int T = 0>
 __device__ __forceinline__ void gather_pairs(const float* xr, int base, int h, float* out) {

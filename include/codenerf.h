@@ -83,6 +83,28 @@ typedef void* cn_stream_t; /* hipStream_t */
  *                    other entry point returns CN_EUNSUPPORTED for it.  No training or backward form
  *                    (their gradients need feat and fc_out's input gradient). */
 #define CN_FMT_F32_W16_FOLD 6
+/*   CN_FMT_F16       fp16 fragments, one product per GEMM on v_mfma_f32_32x32x16_f16 with fp32
+ *                    accumulation: the opt-in fast inference kernel (precision "f16"), NOT the
+ *                    reference's arithmetic.  The rule (tests/field_f16_cases.py states it in float64):
+ *                      - the six GEMM weight matrices -- layer_xyz1, layer_xyz2[:, :256],
+ *                        fc_out[1:, :256], layer_dir1, layer_dir2, fc_rgb[:, :256] -- are rounded to
+ *                        fp16, round to nearest even, once at pack time;
+ *                      - every vector an MFMA reads -- the 63 position encodings, h1, h2, feat, the 27
+ *                        view encodings, v1, v2 -- is rounded to fp16 (RNE) where it is read; a value
+ *                        beyond the fp16 range becomes +-inf;
+ *                      - everything else is fp32 and unrounded: the encodings' own arithmetic, every
+ *                        bias (the accumulators start from the fp32 values), the per-code terms of
+ *                        cn_code_bias (unchanged, stride CN_CODE_BIAS_STRIDE) and the accumulation,
+ *                        whose order is not specified;
+ *                      - sigma_raw (fc_out row 0) is an fp32 dot product of the fp32 weights with the
+ *                        unrounded h2, plus its per-code term, in every input mode;
+ *                      - ReLU is max(x, 0) with a NaN giving 0 (v_max_f32).
+ *                    The pack holds the fp16 fragments (36 chunks of 16 KiB) and 1024 fp32 constants in
+ *                    a float buffer of cn_mlp_packed_floats(CN_FMT_F16) floats.  cn_mlp_forward and
+ *                    cn_radiance_field run it in all their forms; it has no mask, training, backward,
+ *                    density, counted or folded form: those entries refuse it as they refuse
+ *                    CN_FMT_BF16X3_W16. */
+#define CN_FMT_F16 7
 
 const char* cn_version(void);
 const char* cn_error_string(int code);
