@@ -42,6 +42,29 @@ inline unsigned elementwise_grid(int64_t n, int block) {
   return static_cast<unsigned>(g);
 }
 
+// Compute units of the current device (256 if the query fails), cached per device for the whole
+// library.
+inline int64_t cu_count() {
+  static int n[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (n[dev] == 0) {
+    int v = 0;
+    n[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+  }
+  return n[dev];
+}
+
+// Workgroups of a persistent grid over m rows in tiles of `tile`: one per CU (the kernels hold a
+// CU's LDS and every SIMD's registers), never more than there are tiles, nor than `cap`.
+inline unsigned persistent_grid(int64_t m, int64_t tile, int64_t cap = INT64_MAX) {
+  int64_t g = ceil_div(m, tile);
+  const int64_t cus = cu_count();
+  if (g > cus) g = cus;
+  if (g > cap) g = cap;
+  return static_cast<unsigned>(g);
+}
+
 // Exact fp32 a*b then +c with two roundings (never contracted into an FMA):
 // matches torch's separate mul and add kernels bit for bit.
 __device__ __forceinline__ float mul_add_rn(float a, float b, float c) {

@@ -1,6 +1,8 @@
 // The field's C entry points (include/codenerf.h): argument checks, kernel arguments, the launch.
 // No kernel lives here -- the kernels and their launchers are mlp.hip (fp32 32x32x2), mlp_f32.hip
-// (fp32 16x16x4), mlp_x3.hip and mlp_x3w.hip (3xbf16), mlp_f16.hip (fp16, inference only).
+// (fp32 16x16x4), mlp_x3.hip and mlp_x3w.hip (3xbf16), mlp_f16.hip (fp16, inference only).  What the
+// launchers share is in mlp_common.h (the mode dispatch) and cn_common.h (the persistent grid); what
+// the streamed kernels share is in mlp_stream.h.
 //
 // Every entry that takes a field call's geometry, codes and frequency tables gets their checks and its
 // FieldArgs from field_args (encoded rows: encoded_args) and states only what is its own: its buffers,

@@ -362,13 +362,8 @@ int launch_code_bias(const Params& P, const float* z_s, const float* z_t, int64_
 }
 
 int launch_field_v1(int mode, FieldArgs& a, hipStream_t st) {
-  const unsigned grid = static_cast<unsigned>(cn::ceil_div(a.m, kTile));
-  switch (mode) {
-    case kFromPts: hipLaunchKernelGGL(field_kernel<kFromPts>, dim3(grid), dim3(kThreads), 0, st, a); break;
-    case kFromRayZ: hipLaunchKernelGGL(field_kernel<kFromRayZ>, dim3(grid), dim3(kThreads), 0, st, a); break;
-    default: hipLaunchKernelGGL(field_kernel<kFromEncoded>, dim3(grid), dim3(kThreads), 0, st, a); break;
-  }
-  return cn::launch_status();
+  const dim3 grid(static_cast<unsigned>(cn::ceil_div(a.m, kTile))), b(kThreads);
+  return launch_any_mode(mode, [&](auto M) { hipLaunchKernelGGL(field_kernel<M.value>, grid, b, 0, st, a); });
 }
 
 }  // namespace mlp

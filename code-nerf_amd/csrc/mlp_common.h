@@ -3,6 +3,8 @@
 // positional-encoding feature values each lane half owns.
 #pragma once
 
+#include <type_traits>
+
 #include "cn_common.h"
 #include "mlp_layout.h"
 
@@ -292,6 +294,32 @@ __device__ __forceinline__ void code_bias_block(const Params& P, const float* __
     if (lane == 0 && wave + x * kW < nr) o[dst[x]] = a + bv[x];
   }
   if (l == 2 && t >= 3 && t < kCbStride - kCbRgb) o[kCbRgb + t] = 0.f;  // pad 516..519
+}
+
+// The launchers' mode dispatch: the run-time `mode` as a compile-time constant M (M.value) handed to
+// the generic lambda `launch`, which launches its kernel's <M.value, ...> form; the launch status is
+// returned.
+template <int M>
+using ModeConst = std::integral_constant<int, M>;
+
+// A kernel with all three forms: kFromEncoded takes every mode that is not one of the other two (the
+// entry points have checked the range).
+template <typename F>
+inline int launch_any_mode(int mode, F launch) {
+  if (mode == kFromPts) launch(ModeConst<kFromPts>{});
+  else if (mode == kFromRayZ) launch(ModeConst<kFromRayZ>{});
+  else launch(ModeConst<kFromEncoded>{});
+  return cn::launch_status();
+}
+
+// A kernel without a kFromEncoded form (it is never instantiated): any other mode returns
+// `unsupported` before a launch.
+template <typename F>
+inline int launch_ray_mode(int mode, int unsupported, F launch) {
+  if (mode == kFromPts) launch(ModeConst<kFromPts>{});
+  else if (mode == kFromRayZ) launch(ModeConst<kFromRayZ>{});
+  else return unsupported;
+  return cn::launch_status();
 }
 
 // 3xbf16 variant (mlp_x3.hip): forward (optionally writing ReLU masks) and the

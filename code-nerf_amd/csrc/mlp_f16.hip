@@ -18,7 +18,8 @@
 // in the issue gaps of the blocks still running; only the last pair converts in the open.
 //
 // Weight stream.  Chunk = 2 k-steps x 8 blocks x 64 lanes quads = 16 KiB, fragment-major (a wave's
-// ds_read_b128 of one fragment is 1 KiB contiguous); 36 chunks in mlp_x3.hip's order.  A 4-slot LDS
+// ds_read_b128 of one fragment is 1 KiB contiguous); 36 chunks in the order mlp_x3.hip shares with
+// this file (mlp_stream.h: the schedule, the bias paths, the LDS reads and waits).  A 4-slot LDS
 // ring is filled by LDS-DMA, 4 pieces of 1 KiB per wave and chunk.  Chunk c is split by ONE barrier
 // M_c after its 4th MFMA group (of 8): chunk c+1 landed for every wave (counted vmcnt(4): chunk
 // c+2's pieces are the younger ones) and every wave is done with chunk c-1.  Groups 0, 1 of chunk c
@@ -29,55 +30,26 @@
 // Persistent tiles: one workgroup per CU, 128-sample tiles (32 per wave), a cyclic stream (36 chunks,
 // a multiple of the ring) whose last three chunks prefetch the next tile's first three.  The layers
 // are unrolled (a layer is a third of mlp_x3.hip's in instructions).
-#include <algorithm>
-
-#include "mlp_common.h"
+#include "mlp_stream.h"
 
 namespace cn {
 namespace mlp {
 namespace f16 {
 
+using namespace stream;
+using namespace stream32;
+
 typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
 typedef _Float16 halfx2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBlk = 8;                            // 32-row output blocks per k-step
 constexpr int kQuadsPerStep = 64 * kBlk;           // one k-step of a chunk (8 KiB)
 constexpr int kChunkQuads = 2 * kQuadsPerStep;     // 1024 quads = 16 KiB
 constexpr int kDmaPerWave = kChunkQuads / 64 / 4;  // 4
-// stream: xyz1 2 | xyz2 8 | fc_out 8 | layer_dir1 view-dir k-steps 1 | layer_dir1 8 | layer_dir2 8 | fc_rgb 1
-constexpr int kChunkL1 = 2, kChunkL2 = 10, kChunkDir = 18, kChunkL3 = 19, kChunkL4 = 27, kChunkRgb = 35;
-constexpr int kChunks = 36;
 constexpr int kQuads = kChunks * kChunkQuads;
 constexpr int kBiasXyz1 = kQuads * 4;  // floats
-constexpr int kSigmaOff = 768;         // after b_xyz1, b_dir1, b_dir2: fc_out row 0 over h2, [h][b][reg]
-constexpr int kConsts = 1024;
 constexpr int kPackedFloats = kBiasXyz1 + kConsts;
-
-// Input feature of lane half h, element j, k-step s of layer l (-1 = zero pad).
-__host__ __device__ constexpr int in_col(int l, int s, int h, int j) {
-  if (l == kXyz1) return k_from_enc(8 * s + j, h, 15);
-  if (l == kDir1 && s >= 16) {
-    const int t = 8 * (s - 16) + j;
-    if (t >= 14) return -1;
-    const int e = k_from_enc(t, h, 6);
-    return e < 0 ? -1 : kCode + e;
-  }
-  return acc_row(s >> 1, 8 * (s & 1) + j, h);
-}
-
-// (chunk, step-in-chunk T, fragment j) -> (layer, k-step, output block)
-__device__ void chunk_map(int c, int T, int j, int& l, int& ks, int& ob) {
-  ob = j;
-  if (c < kChunkL1) { l = kXyz1; ks = 2 * c + T; }
-  else if (c < kChunkL2) { l = kXyz2; ks = 2 * (c - kChunkL1) + T; }
-  else if (c < kChunkDir) { l = kOut; ks = 2 * (c - kChunkL2) + T; }
-  else if (c == kChunkDir) { l = kDir1; ks = 16 + T; }
-  else if (c < kChunkL4) { l = kDir1; ks = 2 * (c - kChunkL3) + T; }
-  else if (c < kChunkRgb) { l = kDir2; ks = 2 * (c - kChunkL4) + T; }
-  else { l = kRgb; ks = 8 * T + j; ob = 0; }
-}
 
 __global__ void pack_f16_kernel(Params P, float* __restrict__ packed) {
   unsigned short* q16 = reinterpret_cast<unsigned short*>(packed);
@@ -146,17 +118,9 @@ struct State {
   unsigned voff;      // this lane's byte offset inside a 1 KiB-per-wave piece row
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 __device__ __forceinline__ halfx8 b_of(const unsigned* w) {
   const u32x4 u = {w[0], w[1], w[2], w[3]};
   return __builtin_bit_cast(halfx8, u);
-}
-
-__device__ __forceinline__ float vmax(float x, float lo) {
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(lo));
-  return r;
 }
 
 // Two fp32 values -> one dword of fp16 (RNE), pinned where it is written (LLVM would otherwise sink
@@ -172,9 +136,7 @@ __device__ __forceinline__ unsigned pack_pair(float x, float y) {
 // One LDS-DMA piece: 1 KiB per wave (16 B per lane) of chunk `cn`, piece `i` (quads [i*256, i*256+256)
 // of the chunk; this wave moves quads i*256 + wave*64 + lane).
 __device__ __forceinline__ void dma_piece(const State& s, float4* lds, int cn, int i) {
-  const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(cn * kChunkQuads + i * 256) * 16u);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(s.wsrc, (lds_ptr_t)(lds + (cn & (kRing - 1)) * kChunkQuads + i * 256 + s.wave * 64),
-                                           16, s.voff, soff, 0, 0);
+  dma_quads<kChunkQuads, kRing>(s.wsrc, s.wave, s.voff, lds, cn, cn, i * 256);
 }
 
 // The pieces running chunk c issues: groups 0, 1 pieces 2, 3 of chunk c+2, groups 4, 5 pieces 0, 1 of
@@ -193,99 +155,16 @@ template <int G>
 constexpr bool has_piece() { return G < 2 || G == 4 || G == 5; }
 
 __device__ __forceinline__ Dma dma_for(const State& s, float4* lds, int c) {
-  const int ca = c + 2 < kChunks ? c + 2 : c + 2 - kChunks;
-  const int cb = c + 3 < kChunks ? c + 3 : c + 3 - kChunks;
-  return Dma{s, lds, ca, cb};
+  return Dma{s, lds, wrap_chunk(c + 2), wrap_chunk(c + 3)};
 }
 
-// M_c: chunk c+1 landed for every wave (all but this wave's 4 youngest DMA pieces, chunk c+2's,
-// retired), every wave is past chunk c-1, and every LDS read of this wave has returned.  One asm
-// statement, so no LDS read can be scheduled across it.
-__device__ __forceinline__ void chunk_barrier() {
-  asm volatile("s_waitcnt vmcnt(4)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// Small LDS reads outside the ring (biases, sigma weights).  Inline asm: hipcc cannot prove them
-// disjoint from the in-flight DMA and would otherwise wait vmcnt(0), draining the ring.
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return static_cast<unsigned>(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) void*)p));
-}
-
-// 8 floats at p + 32*ob (ob = 0..7), one LDS round trip.
-__device__ __forceinline__ void lds_read8_stride32(const float* p, float* v) {
-  asm volatile(
-      "ds_read_b32 %0, %8\n\tds_read_b32 %1, %8 offset:128\n\tds_read_b32 %2, %8 offset:256\n\t"
-      "ds_read_b32 %3, %8 offset:384\n\tds_read_b32 %4, %8 offset:512\n\tds_read_b32 %5, %8 offset:640\n\t"
-      "ds_read_b32 %6, %8 offset:768\n\tds_read_b32 %7, %8 offset:896\n\ts_waitcnt lgkmcnt(0)"
-      : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
-      : "v"(lds_addr(p))
-      : "memory");
-}
-
-// 16 consecutive floats (64 B aligned), one LDS round trip.
-__device__ __forceinline__ void lds_read16(const float* p, float* v) {
-  u32x4 a, b, c, d;
-  asm volatile(
-      "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\t"
-      "ds_read_b128 %3, %4 offset:48\n\ts_waitcnt lgkmcnt(0)"
-      : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d)
-      : "v"(lds_addr(p))
-      : "memory");
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[i] = __uint_as_float(a[i]);
-    v[4 + i] = __uint_as_float(b[i]);
-    v[8 + i] = __uint_as_float(c[i]);
-    v[12 + i] = __uint_as_float(d[i]);
-  }
-}
-
-__device__ __forceinline__ float lds_read1(const float* p) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(lds_addr(p)) : "memory");
-  return v;
-}
+// M_c is chunk_barrier<kMidOut>: chunk c+2's 4 pieces are the younger ones.
+constexpr int kMidOut = 4;
 
 // Biases.  acc starts as the fp32 value b through ONE fp32 MFMA per output block: A holds b_i at
 // k = 0 (lane half 0), B holds 1.0 at k = 0, so D = b exactly -- no 16-bit operand is involved.
 __device__ __forceinline__ floatx16 bias_mfma(const State& s, float v) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(s.h == 0 ? v : 0.0f, s.h == 0 ? 1.0f : 0.0f, floatx16{0}, 0, 0, 0);
-}
-
-// Bias vector of `layer` for this lane's 8 blocks.
-__device__ __forceinline__ void bias_values(const State& s, const float* blds, int layer, float* v) {
-  const bool per_code = (layer == kXyz2 || layer == kOut);
-  const float* src = per_code ? blds + kConsts + s.wave * kCbStride + (layer == kXyz2 ? kCbXyz2 : kCbFeat)
-                              : blds + (layer == kXyz1 ? 0 : (layer == kDir1 ? 256 : 512));
-  lds_read8_stride32(src + (s.lane & 31), v);
-}
-
-// Slow path (a wave whose samples use several code rows): per-lane loads.
-__device__ __forceinline__ void init_acc_per_lane(State& s, const FieldArgs& a, int layer) {
-  const float* base = a.code_bias + (int64_t)s.crow * kCbStride;
-  if (layer == kRgb) {
-    s.acc[0] = floatx16{0};
-    if (s.h == 0) {
-      s.acc[0][0] = base[kCbRgb];
-      s.acc[0][1] = base[kCbRgb + 1];
-      s.acc[0][2] = base[kCbRgb + 2];
-    }
-  } else {
-    const float* b = base + (layer == kXyz2 ? kCbXyz2 : kCbFeat);
-#pragma unroll
-    for (int ob = 0; ob < 8; ++ob) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 v = *reinterpret_cast<const float4*>(b + 32 * ob + 8 * q + 4 * s.h);
-        s.acc[ob][4 * q + 0] = v.x;
-        s.acc[ob][4 * q + 1] = v.y;
-        s.acc[ob][4 * q + 2] = v.z;
-        s.acc[ob][4 * q + 3] = v.w;
-      }
-    }
-  }
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): nothing pending leaks out
 }
 
 template <int LAYER>
@@ -403,7 +282,7 @@ __device__ __forceinline__ void run_chunk(State& s, float4* lds, int& c, halfx8 
     fill.template step<(G)>();                                                             \
     group_pattern<Fill::kValu, true, has_piece<(G)>()>();                                  \
     __builtin_amdgcn_sched_barrier(0);                                                     \
-    if constexpr ((G) == 3) chunk_barrier();                                               \
+    if constexpr ((G) == 3) chunk_barrier<kMidOut>();                                      \
   }
   CN_GROUP(0, a0, a1)
   CN_GROUP(1, a1, a0)
@@ -542,7 +421,7 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
     s.acc[(2 * (G)) & 3] = mfma(f0, b_of(s.hb[G]), s.acc[(2 * (G)) & 3]);                                  \
     s.acc[(2 * (G) + 1) & 3] = mfma(f1, b_of(s.hb[G] + 4), s.acc[(2 * (G) + 1) & 3]);                      \
     dma.template piece<(G)>();                                                                             \
-    if constexpr ((G) == 3) chunk_barrier();                                                               \
+    if constexpr ((G) == 3) chunk_barrier<kMidOut>();                                                      \
   }
     CN_RGB(0) CN_RGB(1) CN_RGB(2) CN_RGB(3) CN_RGB(4) CN_RGB(5) CN_RGB(6) CN_RGB(7)
 #undef CN_RGB
@@ -594,7 +473,6 @@ __global__ __launch_bounds__(kThreads, 1) void field_f16_kernel(FieldArgs a) {
   __builtin_amdgcn_s_waitcnt(0x0F70);
 }
 
-static_assert(kChunkRgb + 1 == kChunks, "chunk schedule");
 static_assert(kDmaPerWave == 4, "DMA pieces per wave and chunk: groups 0, 1, 4, 5");
 static_assert(kChunks % kRing == 0, "cyclic stream: chunk c + 36 reuses chunk c's ring slot");
 static_assert(kBiasLds * 4 + kLdsQuads * 16 <= 160 * 1024, "LDS budget");
@@ -610,26 +488,11 @@ int launch_pack_f16(const Params& P, float* packed, hipStream_t st) {
   return cn::launch_status();
 }
 
-// Workgroups of the persistent grid: one per CU, never more than there are tiles.
-static int64_t cu_count_f16() {
-  static int n[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (n[dev] == 0) {
-    int v = 0;
-    n[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return n[dev];
-}
-
 int launch_field_f16(int mode, FieldArgs& a, hipStream_t st) {
-  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(a.m, f16::kTile), cu_count_f16()));
-  switch (mode) {
-    case kFromPts: hipLaunchKernelGGL(f16::field_f16_kernel<kFromPts>, dim3(grid), dim3(f16::kThreads), 0, st, a); break;
-    case kFromRayZ: hipLaunchKernelGGL(f16::field_f16_kernel<kFromRayZ>, dim3(grid), dim3(f16::kThreads), 0, st, a); break;
-    default: hipLaunchKernelGGL(f16::field_f16_kernel<kFromEncoded>, dim3(grid), dim3(f16::kThreads), 0, st, a); break;
-  }
-  return cn::launch_status();
+  const dim3 grid(cn::persistent_grid(a.m, f16::kTile)), b(f16::kThreads);
+  return launch_any_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL(f16::field_f16_kernel<M.value>, grid, b, 0, st, a);
+  });
 }
 
 }  // namespace mlp

@@ -27,7 +27,8 @@
 // per chunk).  One barrier M_c in the middle of chunk c: chunk c+1 has landed (counted
 // vmcnt) and every wave is done with chunk c-1, whose slot then receives chunk c+3.  The
 // first A fragments of chunk c+1 are read during chunk c's last k-step, so the matrix
-// pipe never waits on a chunk boundary.  The stream is cyclic across tiles.
+// pipe never waits on a chunk boundary.  The stream is cyclic across tiles.  The tile, the chunk
+// order, the constants and the encoding maps are shared with mlp_x3w.hip (mlp_stream.h).
 //
 // sigma (fc_out row 0) is an fp32 dot product over layer_xyz2's outputs taken in the
 // xyz2 epilogue (32 packed FMAs per lane + a 4-group butterfly); fc_rgb the same way for its
@@ -35,32 +36,24 @@
 // MFMA block over 64 k-steps (r03, removed) 13 of its 16 rows were padding.
 #include <algorithm>
 
-#include "mlp_common.h"
+#include "mlp_stream.h"
 
 namespace cn {
 namespace mlp {
 namespace w16 {
 
+using namespace stream;
+using namespace stream16;
+
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef unsigned uint4v __attribute__((ext_vector_type(4)));
 typedef unsigned uint2v __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-constexpr int kWaves = 8;
-constexpr int kThreads = 64 * kWaves;
-constexpr int kTile = 16 * kWaves;            // samples per workgroup tile
+// the tile, the stream's chunk order, its constants and the encoding maps: stream16 (mlp_stream.h)
 constexpr int kStepQuads = 16 * 64 / 4;       // one 16-block k-step: 256 float4 (4 KiB)
 constexpr int kChunkSteps = 8;
-constexpr int kChunkQuads = kChunkSteps * kStepQuads;   // 2048 float4 = 32 KiB
-constexpr int kRing = 4;
-constexpr int kPiecesPerWave = kChunkQuads / (64 * kWaves);   // 4 x 1 KiB per wave per chunk
-// the stream: xyz1 2 | xyz2 8 | fc_out 8 | dir1 8 | dir1 view-dir 1 | dir2 8 | rgb 1
-constexpr int kCL2 = 2, kCL3 = 10, kCL4 = 18, kCDir = 26, kCL5 = 27, kCRgb = 35, kChunks = 36;
-constexpr int kStreamFloats = kChunks * kChunkQuads * 4;
+static_assert(kChunkSteps * kStepQuads == kChunkQuads, "a chunk is 8 k-steps");
 constexpr int kRgbValu = 64 * 64;  // float offset of fc_rgb's VALU-form rows inside the rgb chunk
-// constants after the stream: b_xyz1 | b_dir1 | b_dir2 | sigma weights (fc_out row 0 over
-// h2, [g][ob][r] = W_out[0][16 ob + 4 g + r])
-constexpr int kCB1 = 0, kCBD1 = 256, kCBD2 = 512, kCSig = 768, kConsts = 1024;
 constexpr int kPackedFloats = kStreamFloats + kConsts;
 // LDS constants: the packed ones, then the encoding frequencies (fx[10] | fd[4] | pad 2): a
 // lane-varying index into the kernel arguments is a global load per use (or a register held
@@ -69,12 +62,9 @@ constexpr int kCFreq = kConsts, kLdsConsts = kConsts + 16;
 // LDS: the ring, the constants, one code-bias row per wave
 constexpr int kLdsQuads = kRing * kChunkQuads + (kLdsConsts + kWaves * kCbStride) / 4;
 
-static_assert(kChunks % kRing == 0, "cyclic stream: chunk c + 36 reuses chunk c's ring slot");
-__host__ __device__ constexpr int col_enc_xyz(int t, int g);
 constexpr bool xenc_map_ok(int cp = 0) {
   return cp == 64 || (xenc_col(cp) == col_enc_xyz(cp & 15, cp >> 4) && xenc_map_ok(cp + 1));
 }
-static_assert(kPiecesPerWave == 4, "4 DMA wave-instructions per chunk per wave");
 static_assert(kLdsQuads * 16 <= 160 * 1024, "LDS budget");
 
 // ---------------------------------------------------------------- feature maps
@@ -82,27 +72,7 @@ static_assert(kLdsQuads * 16 <= 160 * 1024, "LDS budget");
 // Input feature (256-wide previous-layer output) fed at k-step t by lane group g.
 __host__ __device__ constexpr int col_acc(int t, int g) { return 16 * (t >> 2) + 4 * g + (t & 3); }
 
-// xyz encoding column (position_embed.py:44-53: x_d -> d, sin(f_k x_d) -> 3+6k+d,
-// cos(f_k x_d) -> 6+6k+d) fed at k-step t (0..15) by lane group g: sines of pairs
-// p = 4i + g at t = i, cosines at t = 8 + i; groups 2, 3 have 7 pairs and put the raw
-// inputs in the free k-steps 7 / 15 (x0, x1 | x2, pad).
-__host__ __device__ constexpr int col_enc_xyz(int t, int g) {
-  const int i = t & 7, p = 4 * i + g;
-  if (p < 30) return (t < 8 ? 3 : 6) + 6 * (p / 3) + p % 3;
-  return t < 8 ? (g == 2 ? 0 : 2) : (g == 2 ? 1 : -1);
-}
-
 static_assert(xenc_map_ok(), "the encoding plane's column map is layer_xyz1's k-step feature map");
-
-// View-direction encoding column (27 wide) at k-step s (0..6) of the view-dir chunk:
-// sines of pairs p = 4i + g at s = i (i < 3), cosines at s = 3 + i, raw component g at s = 6.
-__host__ __device__ constexpr int col_enc_dir(int s, int g) {
-  if (s < 6) {
-    const int p = 4 * (s % 3) + g;
-    return (s < 3 ? 3 : 6) + 6 * (p / 3) + p % 3;
-  }
-  return (s == 6 && g < 3) ? g : -1;
-}
 
 // ---------------------------------------------------------------- packing
 
@@ -365,8 +335,8 @@ __device__ __forceinline__ void dma_chunk(const State& s, float4* lds, int cn) {
   for (int p = 0; p < kPiecesPerWave; ++p) dma_piece<NG>(s, lds, cn, p);
 }
 
-// M_c: chunk c+1 landed for every wave (all but this wave's 4 youngest DMA pieces --
-// chunk c+2's -- retired), every wave past chunk c-1, this wave's LDS reads returned.
+// M_c (chunk_barrier<kMidOut>): chunk c+1 landed for every wave (all but this wave's 4 youngest DMA
+// pieces -- chunk c+2's -- retired), every wave past chunk c-1, this wave's LDS reads returned.
 //
 // The folded table variant (kStreamRows) issues chunk c+3's pieces one per k-step in k-steps 4..7 of chunk
 // c, behind each k-step's MFMAs, instead of all four right after M_c, where all 8 waves -- both waves of
@@ -387,10 +357,7 @@ __device__ __forceinline__ void dma_chunk(const State& s, float4* lds, int cn) {
 // No piece of chunk c+3 targets a slot in use: its slot is chunk c-1's, whose last read precedes M_c in
 // every wave, and the pieces follow M_c.  The tile head waits for nothing; the trailing vmcnt(0) before
 // the workgroup ends stays.
-__device__ __forceinline__ void chunk_barrier() {
-  asm volatile("s_waitcnt vmcnt(4)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
+constexpr int kMidOut = 4;
 
 // A fragments of k-step T (16 blocks) of the chunk at `slot` (float4 units, lane applied).
 template <int T>
@@ -470,7 +437,7 @@ __device__ __forceinline__ void chunk16(State& s, float4* lds, int c, GetB getb,
     else step_pattern();                                            \
     __builtin_amdgcn_sched_barrier(0);                              \
     if constexpr ((T) == 3) {                                       \
-      chunk_barrier();                                              \
+      chunk_barrier<kMidOut>();                                              \
       post.template before_dma<CI>();                               \
       if constexpr (NG != kStreamRows) dma_chunk<NG>(s, lds, c + 3); \
     }                                                               \
@@ -1161,7 +1128,7 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
       }
     };
     blocks(std::integral_constant<int, 0>{});
-    chunk_barrier();
+    chunk_barrier<kMidOut>();
     dma_chunk<NG>(s, lds, c + 3);
     st_v2.template blocks<0, 8>();
     blocks(std::integral_constant<int, 8>{});
@@ -1744,10 +1711,6 @@ __device__ __forceinline__ void rowsum64(const floatx4* v, float* out, int i) {
 
 __device__ __forceinline__ int rev4(int i) { return ((i & 1) << 3) | ((i & 2) << 1) | ((i & 4) >> 1) | ((i & 8) >> 3); }
 
-__device__ __forceinline__ unsigned lds_addr(const float* p) {
-  return static_cast<unsigned>(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) float*)(p)));
-}
-
 // row[COL + 16 ob + 4 g + r] += sum over the wave's samples of v[ob][r] (all 64 features of this
 // lane group; `row`: an LDS row, wave-uniform).  The 4 float atomics per lane are issued by inline
 // asm: for a compiler-visible LDS write hipcc cannot rule out the in-flight LDS-DMA ring writes
@@ -1803,7 +1766,7 @@ __device__ __forceinline__ void chunk_k0(State& s, float4* lds, int c, float b, 
 #pragma unroll
   for (int q = 0; q < 4; ++q) a0[q] = s.pre[q];
   __builtin_amdgcn_sched_barrier(0);
-  chunk_barrier();
+  chunk_barrier<kMidOut>();
   dma_chunk<X1STORE>(s, lds, c + 3);
   read_a<0>(nslot, s.pre);
   if constexpr (X1STORE) store_plane<0, 16>(s, x1, s.act);
@@ -1845,7 +1808,7 @@ __device__ __forceinline__ void chunk_narrow(State& s, float4* lds, int c, Post 
     step_pattern();                                                 \
     __builtin_amdgcn_sched_barrier(0);                              \
     if constexpr ((T) == 3) {                                       \
-      chunk_barrier();                                              \
+      chunk_barrier<kMidOut>();                                              \
       dma_chunk<NG>(s, lds, c + 3);                                 \
     }                                                               \
     post.template step<CI, (T)>();                                  \
@@ -2370,17 +2333,6 @@ __global__ __launch_bounds__(kThreads, 2) void density_grad_w16_kernel(DensityGr
 
 }  // namespace w16
 
-static int64_t cu_count_w16() {
-  static int n[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (n[dev] == 0) {
-    int v = 0;
-    n[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return n[dev];
-}
-
 int64_t packed_floats_w16() { return w16::kPackedFloats; }
 
 int launch_pack_w16(const Params& P, float* packed, hipStream_t st) {
@@ -2390,26 +2342,18 @@ int launch_pack_w16(const Params& P, float* packed, hipStream_t st) {
 }
 
 int launch_field_w16(int mode, FieldArgs& a, hipStream_t st) {
-  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(a.m, w16::kTile), cu_count_w16()));
-  const dim3 b(w16::kThreads);
-  if (a.masks && a.save) {
-    if (mode == kFromPts) hipLaunchKernelGGL((w16::field_w16_kernel<kFromPts, true, true>), dim3(grid), b, 0, st, a);
-    else if (mode == kFromRayZ) hipLaunchKernelGGL((w16::field_w16_kernel<kFromRayZ, true, true>), dim3(grid), b, 0, st, a);
-    else return CN_EUNSUPPORTED;
-    return cn::launch_status();
-  }
-  if (a.masks) {
-    if (mode == kFromPts) hipLaunchKernelGGL((w16::field_w16_kernel<kFromPts, true>), dim3(grid), b, 0, st, a);
-    else if (mode == kFromRayZ) hipLaunchKernelGGL((w16::field_w16_kernel<kFromRayZ, true>), dim3(grid), b, 0, st, a);
-    else return CN_EUNSUPPORTED;
-    return cn::launch_status();
-  }
-  switch (mode) {
-    case kFromPts: hipLaunchKernelGGL((w16::field_w16_kernel<kFromPts, false>), dim3(grid), b, 0, st, a); break;
-    case kFromRayZ: hipLaunchKernelGGL((w16::field_w16_kernel<kFromRayZ, false>), dim3(grid), b, 0, st, a); break;
-    default: hipLaunchKernelGGL((w16::field_w16_kernel<kFromEncoded, false>), dim3(grid), b, 0, st, a); break;
-  }
-  return cn::launch_status();
+  const dim3 grid(cn::persistent_grid(a.m, w16::kTile)), b(w16::kThreads);
+  if (a.masks && a.save)
+    return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+      hipLaunchKernelGGL((w16::field_w16_kernel<M.value, true, true>), grid, b, 0, st, a);
+    });
+  if (a.masks)
+    return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+      hipLaunchKernelGGL((w16::field_w16_kernel<M.value, true>), grid, b, 0, st, a);
+    });
+  return launch_any_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL((w16::field_w16_kernel<M.value, false>), grid, b, 0, st, a);
+  });
 }
 
 int64_t packed_floats_w16_fold() { return w16::kFoldPackedFloats; }
@@ -2428,14 +2372,10 @@ int launch_fold_bias(const Params& P, const float* code_bias, int64_t n_codes, f
 
 int launch_field_w16_fold(int mode, FieldArgs& a, hipStream_t st) {
   if (!a.fold_bias || a.masks || a.save) return CN_EINVAL;
-  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(a.m, w16::kTile), cu_count_w16()));
-  const dim3 b(w16::kThreads);
-  switch (mode) {
-    case kFromPts: hipLaunchKernelGGL((w16::field_w16_kernel<kFromPts, false, false, true>), dim3(grid), b, 0, st, a); break;
-    case kFromRayZ: hipLaunchKernelGGL((w16::field_w16_kernel<kFromRayZ, false, false, true>), dim3(grid), b, 0, st, a); break;
-    default: hipLaunchKernelGGL((w16::field_w16_kernel<kFromEncoded, false, false, true>), dim3(grid), b, 0, st, a); break;
-  }
-  return cn::launch_status();
+  const dim3 grid(cn::persistent_grid(a.m, w16::kTile)), b(w16::kThreads);
+  return launch_any_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL((w16::field_w16_kernel<M.value, false, false, true>), grid, b, 0, st, a);
+  });
 }
 
 int launch_view_rows_w16(FieldArgs& a, float* rows, hipStream_t st) {
@@ -2448,25 +2388,17 @@ int launch_view_rows_w16(FieldArgs& a, float* rows, hipStream_t st) {
 
 int launch_field_w16_fold_rows(int mode, FieldArgs& a, hipStream_t st) {
   if (!a.fold_bias || !a.view_rows || a.masks || a.save || a.n_codes != 1 || a.code_index) return CN_EINVAL;
-  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(a.m, w16::kTile), cu_count_w16()));
-  const dim3 b(w16::kThreads);
-  switch (mode) {
-    case kFromPts: hipLaunchKernelGGL((w16::field_w16_kernel<kFromPts, false, false, true, true>), dim3(grid), b, 0, st, a); break;
-    case kFromRayZ: hipLaunchKernelGGL((w16::field_w16_kernel<kFromRayZ, false, false, true, true>), dim3(grid), b, 0, st, a); break;
-    default: return CN_EINVAL;
-  }
-  return cn::launch_status();
+  const dim3 grid(cn::persistent_grid(a.m, w16::kTile)), b(w16::kThreads);
+  return launch_ray_mode(mode, CN_EINVAL, [&](auto M) {
+    hipLaunchKernelGGL((w16::field_w16_kernel<M.value, false, false, true, true>), grid, b, 0, st, a);
+  });
 }
 
 int launch_density_w16(int mode, DensityArgs& d, hipStream_t st) {
-  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(d.f.m, w16::kTile), cu_count_w16()));
-  const dim3 b(w16::kThreads);
-  switch (mode) {
-    case kFromPts: hipLaunchKernelGGL((w16::density_w16_kernel<kFromPts>), dim3(grid), b, 0, st, d); break;
-    case kFromRayZ: hipLaunchKernelGGL((w16::density_w16_kernel<kFromRayZ>), dim3(grid), b, 0, st, d); break;
-    default: hipLaunchKernelGGL((w16::density_w16_kernel<kFromEncoded>), dim3(grid), b, 0, st, d); break;
-  }
-  return cn::launch_status();
+  const dim3 grid(cn::persistent_grid(d.f.m, w16::kTile)), b(w16::kThreads);
+  return launch_any_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL(w16::density_w16_kernel<M.value>, grid, b, 0, st, d);
+  });
 }
 
 // The counted launches (points form, a.m = the capacity): the grid of a launch over a.m rows -- the
@@ -2474,28 +2406,25 @@ int launch_density_w16(int mode, DensityArgs& d, hipStream_t st) {
 int launch_field_w16_counted(bool fold, FieldArgs& a, const int64_t* count, hipStream_t st) {
   if (!count || !a.pts || a.n_samples != 1 || a.masks || a.save || a.view_rows || (fold && !a.fold_bias))
     return CN_EINVAL;
-  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(a.m, w16::kTile), cu_count_w16()));
-  const dim3 b(w16::kThreads);
-  if (fold) hipLaunchKernelGGL((w16::field_w16_counted_kernel<true>), dim3(grid), b, 0, st, a, count);
-  else hipLaunchKernelGGL((w16::field_w16_counted_kernel<false>), dim3(grid), b, 0, st, a, count);
+  const dim3 grid(cn::persistent_grid(a.m, w16::kTile)), b(w16::kThreads);
+  if (fold) hipLaunchKernelGGL((w16::field_w16_counted_kernel<true>), grid, b, 0, st, a, count);
+  else hipLaunchKernelGGL((w16::field_w16_counted_kernel<false>), grid, b, 0, st, a, count);
   return cn::launch_status();
 }
 
 int launch_density_w16_counted(DensityArgs& d, const int64_t* count, hipStream_t st) {
   if (!count || !d.f.pts || d.f.n_samples != 1) return CN_EINVAL;
-  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(d.f.m, w16::kTile), cu_count_w16()));
-  hipLaunchKernelGGL(w16::density_w16_counted_kernel, dim3(grid), dim3(w16::kThreads), 0, st, d, count);
+  hipLaunchKernelGGL(w16::density_w16_counted_kernel, dim3(cn::persistent_grid(d.f.m, w16::kTile)), dim3(w16::kThreads),
+                     0, st, d, count);
   return cn::launch_status();
 }
 
 int launch_density_grad_w16(int mode, DensityArgs& d, const float* packed_t, hipStream_t st) {
-  if (mode != kFromPts && mode != kFromRayZ) return CN_EINVAL;
-  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(d.f.m, w16::kTile), cu_count_w16()));
-  const dim3 b(w16::kThreads);
+  const dim3 grid(cn::persistent_grid(d.f.m, w16::kTile)), b(w16::kThreads);
   const w16::DensityGradArgs ga{d, packed_t};
-  if (mode == kFromPts) hipLaunchKernelGGL((w16::density_grad_w16_kernel<kFromPts>), dim3(grid), b, 0, st, ga);
-  else hipLaunchKernelGGL((w16::density_grad_w16_kernel<kFromRayZ>), dim3(grid), b, 0, st, ga);
-  return cn::launch_status();
+  return launch_ray_mode(mode, CN_EINVAL, [&](auto M) {
+    hipLaunchKernelGGL(w16::density_grad_w16_kernel<M.value>, grid, b, 0, st, ga);
+  });
 }
 
 int64_t mask_words_w16(int64_t m) { return cn::ceil_div(m, w16::kTile) * w16::kMaskWordsPerTile; }
@@ -2529,11 +2458,6 @@ int launch_pack_w16t(const Params& P, float* packed, hipStream_t st) {
   return cn::launch_status();
 }
 
-static unsigned bwd_grid_w16(const FieldArgs& a) {
-  return static_cast<unsigned>(
-      std::min<int64_t>(std::min<int64_t>(cn::ceil_div(a.m, w16::kTile), cu_count_w16()), kMaxBwdBlocks));
-}
-
 // Two fields' fused backwards in one launch (field_w16_bwd2_kernel): both must take the same kernel form
 // (the same mode, training / no-geometry / deterministic choice), else CN_EUNSUPPORTED before any launch.
 int launch_field_w16_bwd2(int mode, FieldArgs& a0, FieldArgs& a1, hipStream_t st) {
@@ -2543,7 +2467,8 @@ int launch_field_w16_bwd2(int mode, FieldArgs& a0, FieldArgs& a1, hipStream_t st
   };
   const int f = form(a0);
   if (form(a1) != f || mode != kFromRayZ) return CN_EUNSUPPORTED;
-  const unsigned g0 = bwd_grid_w16(a0), g1 = bwd_grid_w16(a1);
+  const unsigned g0 = cn::persistent_grid(a0.m, w16::kTile, kMaxBwdBlocks);
+  const unsigned g1 = cn::persistent_grid(a1.m, w16::kTile, kMaxBwdBlocks);
   a0.n_blocks = g0;
   a1.n_blocks = g1;
   const dim3 grid(g0 + g1), b(w16::kThreads);
@@ -2557,33 +2482,24 @@ int launch_field_w16_bwd2(int mode, FieldArgs& a0, FieldArgs& a1, hipStream_t st
 }
 
 int launch_field_w16_bwd(int mode, FieldArgs& a, hipStream_t st) {
-  const unsigned grid = static_cast<unsigned>(
-      std::min<int64_t>(std::min<int64_t>(cn::ceil_div(a.m, w16::kTile), cu_count_w16()), kMaxBwdBlocks));
-  a.n_blocks = grid;
-  const dim3 b(w16::kThreads);
+  const dim3 grid(cn::persistent_grid(a.m, w16::kTile, kMaxBwdBlocks)), b(w16::kThreads);
+  a.n_blocks = grid.x;
   // training with no geometry gradient wanted (train.py: the rays are data): the 33-chunk schedule
-  if (a.dpre && !a.d_pts && !a.d_ro && !a.d_rd) {
-    if (mode == kFromPts) hipLaunchKernelGGL((w16::field_w16_bwd_kernel<kFromPts, true, true>), dim3(grid), b, 0, st, a);
-    else if (mode == kFromRayZ) hipLaunchKernelGGL((w16::field_w16_bwd_kernel<kFromRayZ, true, true>), dim3(grid), b, 0, st, a);
-    else return CN_EUNSUPPORTED;
-    return cn::launch_status();
-  }
-  if (a.dpre) {
-    if (mode == kFromPts) hipLaunchKernelGGL((w16::field_w16_bwd_kernel<kFromPts, true>), dim3(grid), b, 0, st, a);
-    else if (mode == kFromRayZ) hipLaunchKernelGGL((w16::field_w16_bwd_kernel<kFromRayZ, true>), dim3(grid), b, 0, st, a);
-    else return CN_EUNSUPPORTED;
-    return cn::launch_status();
-  }
-  if (a.gc_part) {   // the eval backward without float atomics (cn_field_backward_fused_ws)
-    if (mode == kFromPts) hipLaunchKernelGGL((w16::field_w16_bwd_kernel<kFromPts, false, false, true>), dim3(grid), b, 0, st, a);
-    else if (mode == kFromRayZ) hipLaunchKernelGGL((w16::field_w16_bwd_kernel<kFromRayZ, false, false, true>), dim3(grid), b, 0, st, a);
-    else return CN_EUNSUPPORTED;
-    return cn::launch_status();
-  }
-  if (mode == kFromPts) hipLaunchKernelGGL((w16::field_w16_bwd_kernel<kFromPts, false>), dim3(grid), b, 0, st, a);
-  else if (mode == kFromRayZ) hipLaunchKernelGGL((w16::field_w16_bwd_kernel<kFromRayZ, false>), dim3(grid), b, 0, st, a);
-  else return CN_EUNSUPPORTED;
-  return cn::launch_status();
+  if (a.dpre && !a.d_pts && !a.d_ro && !a.d_rd)
+    return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+      hipLaunchKernelGGL((w16::field_w16_bwd_kernel<M.value, true, true>), grid, b, 0, st, a);
+    });
+  if (a.dpre)
+    return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+      hipLaunchKernelGGL((w16::field_w16_bwd_kernel<M.value, true>), grid, b, 0, st, a);
+    });
+  if (a.gc_part)   // the eval backward without float atomics (cn_field_backward_fused_ws)
+    return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+      hipLaunchKernelGGL((w16::field_w16_bwd_kernel<M.value, false, false, true>), grid, b, 0, st, a);
+    });
+  return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+    hipLaunchKernelGGL((w16::field_w16_bwd_kernel<M.value, false>), grid, b, 0, st, a);
+  });
 }
 
 }  // namespace mlp

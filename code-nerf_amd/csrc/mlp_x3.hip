@@ -39,64 +39,34 @@
 // slots): the last three chunks of a tile prefetch the first three of the
 // next, so the ring never drains or re-primes between tiles.
 //
+// Shared with mlp_f16.hip (mlp_stream.h): the chunk schedule and its maps, the bias paths, the
+// inline-asm LDS reads, the chunk barrier and the LDS-DMA instruction.
+//
 // Code size.  The four 256-input layers run through ONE runtime loop whose body
 // is a single unrolled 16-k-step layer (a fully unrolled kernel is
 // instruction-fetch bound).
-#include <algorithm>
 #include <type_traits>
 
-#include "mlp_common.h"
+#include "mlp_stream.h"
 
 namespace cn {
 namespace mlp {
 namespace x3 {
 
+using namespace stream;
+using namespace stream32;
+
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBlk = 8;                              // 32-row output blocks per k-step
 constexpr int kQuadsPerStep = 64 * kBlk * 2;         // one k-step of a chunk (16 KiB)
 constexpr int kChunkQuads = 2 * kQuadsPerStep;       // 2048 quads = 32 KiB
 constexpr int kDmaPerWave = kChunkQuads / 64 / 4;    // 8
-// stream: xyz1 2 | xyz2 8 | fc_out 8 | layer_dir1 view-dir k-steps 1 | layer_dir1 8 | layer_dir2 8 | fc_rgb 1
-constexpr int kChunkL1 = 2, kChunkL2 = 10, kChunkDir = 18, kChunkL3 = 19, kChunkL4 = 27, kChunkRgb = 35;
-constexpr int kChunks = 36;
 constexpr int kQuads = kChunks * kChunkQuads;
 constexpr int kBiasXyz1 = kQuads * 4;  // floats
-constexpr int kSigmaOff = 768;         // after b_xyz1, b_dir1, b_dir2: fc_out row 0 over h2, [h][b][reg]
-constexpr int kConsts = 1024;
 constexpr int kPackedFloats = kBiasXyz1 + kConsts;
-
-// Input feature of lane half h, element j, k-step s of layer l (-1 = zero pad).
-__host__ __device__ constexpr int in_col(int l, int s, int h, int j) {
-  if (l == kXyz1) return k_from_enc(8 * s + j, h, 15);
-  if (l == kDir1 && s >= 16) {
-    const int t = 8 * (s - 16) + j;
-    if (t >= 14) return -1;
-    const int e = k_from_enc(t, h, 6);
-    return e < 0 ? -1 : kCode + e;
-  }
-  return acc_row(s >> 1, 8 * (s & 1) + j, h);
-}
-
-__device__ __forceinline__ unsigned short bf16_bits(float x) {
-  const __bf16 b = static_cast<__bf16>(x);
-  return __builtin_bit_cast(unsigned short, b);
-}
-
-// (chunk, step-in-chunk T, slot j) -> (layer, k-step, output block)
-__device__ void chunk_map(int c, int T, int j, int& l, int& ks, int& ob) {
-  ob = j;
-  if (c < kChunkL1) { l = kXyz1; ks = 2 * c + T; }
-  else if (c < kChunkL2) { l = kXyz2; ks = 2 * (c - kChunkL1) + T; }
-  else if (c < kChunkDir) { l = kOut; ks = 2 * (c - kChunkL2) + T; }
-  else if (c == kChunkDir) { l = kDir1; ks = 16 + T; }
-  else if (c < kChunkL4) { l = kDir1; ks = 2 * (c - kChunkL3) + T; }
-  else if (c < kChunkRgb) { l = kDir2; ks = 2 * (c - kChunkL4) + T; }
-  else { l = kRgb; ks = 8 * T + j; ob = 0; }
-}
 
 __global__ void pack_x3_kernel(Params P, float* __restrict__ packed) {
   unsigned short* q16 = reinterpret_cast<unsigned short*>(packed);
@@ -171,8 +141,6 @@ struct State {
   int cbase;              // no-geometry backward: chunk counter at the tile's first chunk (DmaNoGeo)
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 __device__ __forceinline__ bf16x8 dw8(const float* f) {
   const u32x4 u = {__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3])};
   return __builtin_bit_cast(bf16x8, u);
@@ -183,12 +151,6 @@ __device__ __forceinline__ bf16x8 Bh(const State& s, int t) { return dw8(s.sl[J]
 template <int J>
 __device__ __forceinline__ bf16x8 Bl(const State& s, int t) { return dw8(s.sl[J] + 8 * t + 4); }
 #define CN_SLOT_B(J) Bh<J>(s, 0), Bl<J>(s, 0), Bh<J>(s, 1), Bl<J>(s, 1)
-
-__device__ __forceinline__ float vmax(float x, float lo) {
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(lo));
-  return r;
-}
 
 // Values 2K, 2K+1 of a raw block -> activation, hi/lo bf16 into `out` (k-step
 // K/4, dword K%4); sig += w . v (the sigma dot product, kept only in fc_out).
@@ -262,9 +224,7 @@ __device__ __forceinline__ void save_slot(const State& s, float lo) {
 // (piece i of chunk cn covers quads [i*256, i*256+256) of the chunk; this wave
 // moves quads i*256 + wave*64 + lane).
 __device__ __forceinline__ void dma_piece(const State& s, float4* lds, int cn, int i) {
-  const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(cn * kChunkQuads + i * 256) * 16u);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(s.wsrc, (lds_ptr_t)(lds + (cn & (kRing - 1)) * kChunkQuads + i * 256 + s.wave * 64),
-                                           16, s.voff, soff, 0, 0);
+  dma_quads<kChunkQuads, kRing>(s.wsrc, s.wave, s.voff, lds, cn, cn, i * 256);
 }
 
 // The pieces running chunk c issues: groups 0-3 pieces 4-7 of chunk c+2, groups
@@ -282,9 +242,7 @@ struct Dma {
 };
 
 __device__ __forceinline__ Dma dma_for(const State& s, float4* lds, int c) {
-  const int ca = c + 2 < kChunks ? c + 2 : c + 2 - kChunks;
-  const int cb = c + 3 < kChunks ? c + 3 : c + 3 - kChunks;
-  return Dma{s, lds, ca, cb};
+  return Dma{s, lds, wrap_chunk(c + 2), wrap_chunk(c + 3)};
 }
 // The default chunk stream: the 36 chunks from c = 0 in every tile.
 struct DmaFull {
@@ -300,9 +258,7 @@ __device__ __forceinline__ void dma_piece_ng(const State& s, float4* lds, int cn
   int k = cn - s.cbase;
   if (k >= kNoGeoChunks) k -= kNoGeoChunks;
   const int src = k + (k >= kNoGeoSkip ? 1 : 0);
-  const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(src * kChunkQuads + i * 256) * 16u);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(s.wsrc, (lds_ptr_t)(lds + (cn & (kRing - 1)) * kChunkQuads + i * 256 + s.wave * 64),
-                                           16, s.voff, soff, 0, 0);
+  dma_quads<kChunkQuads, kRing>(s.wsrc, s.wave, s.voff, lds, cn, src, i * 256);
 }
 struct DmaNoGeoPieces {
   const State& s;
@@ -320,77 +276,8 @@ struct DmaNoGeo {
   }
 };
 
-// M_c: chunk c+1 landed for every wave (all but this wave's OUT youngest DMA
-// pieces retired), every wave is past chunk c-1, and every LDS read of this
-// wave (incl. the asynchronous sigma-weight reads) has returned.  One asm
-// statement, so no LDS read can be scheduled across it.
-template <int OUT>
-__device__ __forceinline__ void chunk_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(OUT) : "memory");
-  __builtin_amdgcn_sched_barrier(0);  // nothing (ring reads included) is scheduled above the wait
-}
+// M_c is chunk_barrier<kMidOut>.
 constexpr int kMidOut = 8;  // chunk c+2's pieces are younger than chunk c+1's at M_c
-
-// Small LDS reads outside the ring (biases, sigma weights).  Inline asm: hipcc
-// cannot prove them disjoint from the in-flight DMA and would otherwise wait
-// vmcnt(0), draining the ring.
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return static_cast<unsigned>(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) void*)p));
-}
-
-// 8 floats at p + 32*ob (ob = 0..7), one LDS round trip.
-__device__ __forceinline__ void lds_read8_stride32(const float* p, float* v) {
-  asm volatile(
-      "ds_read_b32 %0, %8\n\tds_read_b32 %1, %8 offset:128\n\tds_read_b32 %2, %8 offset:256\n\t"
-      "ds_read_b32 %3, %8 offset:384\n\tds_read_b32 %4, %8 offset:512\n\tds_read_b32 %5, %8 offset:640\n\t"
-      "ds_read_b32 %6, %8 offset:768\n\tds_read_b32 %7, %8 offset:896\n\ts_waitcnt lgkmcnt(0)"
-      : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
-      : "v"(lds_addr(p))
-      : "memory");
-}
-
-// 16 consecutive floats (64 B aligned), one LDS round trip.
-__device__ __forceinline__ void lds_read16(const float* p, float* v) {
-  u32x4 a, b, c, d;
-  asm volatile(
-      "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\t"
-      "ds_read_b128 %3, %4 offset:48\n\ts_waitcnt lgkmcnt(0)"
-      : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d)
-      : "v"(lds_addr(p))
-      : "memory");
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[i] = __uint_as_float(a[i]);
-    v[4 + i] = __uint_as_float(b[i]);
-    v[8 + i] = __uint_as_float(c[i]);
-    v[12 + i] = __uint_as_float(d[i]);
-  }
-}
-
-// The same without a wait: the values are first used after the next chunk
-// barrier, whose lgkmcnt(0) covers them (volatile asm keeps the order).
-__device__ __forceinline__ void lds_read16_async(const float* p, float* v) {
-  u32x4 a, b, c, d;
-  asm volatile(
-      "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\t"
-      "ds_read_b128 %3, %4 offset:48"
-      : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d)
-      : "v"(lds_addr(p))
-      : "memory");
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[i] = __uint_as_float(a[i]);
-    v[4 + i] = __uint_as_float(b[i]);
-    v[8 + i] = __uint_as_float(c[i]);
-    v[12 + i] = __uint_as_float(d[i]);
-  }
-}
-
-__device__ __forceinline__ float lds_read1(const float* p) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(lds_addr(p)) : "memory");
-  return v;
-}
 
 // Biases.  acc starts as b via ONE MFMA per output block: A holds {bf16(b_i),
 // bf16(b_i - hi)} at k = 0, 1 (lane half 0), B holds ones at k = 0, 1, so D = hi
@@ -410,41 +297,6 @@ __device__ __forceinline__ bf16x8 ones_b(int h) {
     one[1] = static_cast<__bf16>(1.0f);
   }
   return one;
-}
-
-// Bias vector of `layer` for this lane's 8 blocks (lane half 0 carries it).
-__device__ __forceinline__ void bias_values(const State& s, const float* blds, int layer, float* v) {
-  const bool per_code = (layer == kXyz2 || layer == kOut);
-  const float* src = per_code ? blds + kConsts + s.wave * kCbStride + (layer == kXyz2 ? kCbXyz2 : kCbFeat)
-                              : blds + (layer == kXyz1 ? 0 : (layer == kDir1 ? 256 : 512));
-  lds_read8_stride32(src + (s.lane & 31), v);
-}
-
-// Slow path (a wave whose samples use several code rows): per-lane loads.
-__device__ __forceinline__ void init_acc_per_lane(State& s, const FieldArgs& a, int layer) {
-  const float* base = a.code_bias + (int64_t)s.crow * kCbStride;
-  if (layer == kRgb) {
-    s.acc[0] = floatx16{0};
-    if (s.h == 0) {
-      s.acc[0][0] = base[kCbRgb];
-      s.acc[0][1] = base[kCbRgb + 1];
-      s.acc[0][2] = base[kCbRgb + 2];
-    }
-  } else {
-    const float* b = base + (layer == kXyz2 ? kCbXyz2 : kCbFeat);
-#pragma unroll
-    for (int ob = 0; ob < 8; ++ob) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 v = *reinterpret_cast<const float4*>(b + 32 * ob + 8 * q + 4 * s.h);
-        s.acc[ob][4 * q + 0] = v.x;
-        s.acc[ob][4 * q + 1] = v.y;
-        s.acc[ob][4 * q + 2] = v.z;
-        s.acc[ob][4 * q + 3] = v.w;
-      }
-    }
-  }
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): nothing pending leaks out
 }
 
 __device__ __forceinline__ void mfma3(floatx16& acc, bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl) {
@@ -861,7 +713,6 @@ __global__ __launch_bounds__(kThreads, 1) void field_x3_kernel(FieldArgs a) {
   __builtin_amdgcn_s_waitcnt(0x0F70);
 }
 
-static_assert(kChunkRgb + 1 == kChunks, "chunk schedule");
 static_assert(kDmaPerWave * 64 * 4 == kChunkQuads, "chunk = 32 DMA wave-instructions");
 static_assert(kDmaPerWave == 8, "one DMA piece per MFMA group (8 groups per chunk)");
 static_assert(kChunks % kRing == 0, "cyclic stream: chunk c + 36 reuses chunk c's ring slot");
@@ -1511,19 +1362,6 @@ int launch_pack_x3(const Params& P, float* packed, hipStream_t st) {
   return cn::launch_status();
 }
 
-// Workgroups of the persistent grid: one per CU (the kernel holds a CU's LDS and
-// every SIMD's registers), never more than there are tiles.
-static int64_t cu_count() {
-  static int n[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (n[dev] == 0) {
-    int v = 0;
-    n[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return n[dev];
-}
-
 int launch_pack_x3t(const Params& P, float* packed, hipStream_t st) {
   const int64_t n = (int64_t)x3::kQuads * 8 + x3::kConsts;
   hipLaunchKernelGGL(x3::pack_x3t_kernel, dim3(cn::elementwise_grid(n, 256)), dim3(256), 0, st, P, packed);
@@ -1533,65 +1371,38 @@ int launch_pack_x3t(const Params& P, float* packed, hipStream_t st) {
 int64_t mask_words_x3(int64_t m) { return cn::ceil_div(m, x3::kTile) * x3::kMaskWordsPerTile; }
 
 int launch_field_x3_bwd(int mode, FieldArgs& a, hipStream_t st) {
-  const unsigned grid = static_cast<unsigned>(
-      std::min<int64_t>(std::min<int64_t>(cn::ceil_div(a.m, x3::kTile), cu_count()), kMaxBwdBlocks));
-  a.n_blocks = grid;
-  if (a.dpre && !a.d_pts && !a.d_ro && !a.d_rd) {   // training, no geometry gradient wanted
-    switch (mode) {
-      case kFromPts: hipLaunchKernelGGL((x3::field_x3_bwd_kernel<kFromPts, true, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-      case kFromRayZ: hipLaunchKernelGGL((x3::field_x3_bwd_kernel<kFromRayZ, true, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-      default: return CN_EUNSUPPORTED;
-    }
-    return cn::launch_status();
-  }
-  if (a.dpre) {
-    switch (mode) {
-      case kFromPts: hipLaunchKernelGGL((x3::field_x3_bwd_kernel<kFromPts, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-      case kFromRayZ: hipLaunchKernelGGL((x3::field_x3_bwd_kernel<kFromRayZ, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-      default: return CN_EUNSUPPORTED;
-    }
-    return cn::launch_status();
-  }
-  if (a.gc_part) {   // the eval backward without float atomics (cn_field_backward_fused_ws)
-    switch (mode) {
-      case kFromPts: hipLaunchKernelGGL((x3::field_x3_bwd_kernel<kFromPts, false, false, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-      case kFromRayZ: hipLaunchKernelGGL((x3::field_x3_bwd_kernel<kFromRayZ, false, false, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-      default: return CN_EUNSUPPORTED;
-    }
-    return cn::launch_status();
-  }
-  switch (mode) {
-    case kFromPts: hipLaunchKernelGGL(x3::field_x3_bwd_kernel<kFromPts>, dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-    case kFromRayZ: hipLaunchKernelGGL(x3::field_x3_bwd_kernel<kFromRayZ>, dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-    default: return CN_EUNSUPPORTED;
-  }
-  return cn::launch_status();
+  const dim3 grid(cn::persistent_grid(a.m, x3::kTile, kMaxBwdBlocks)), b(x3::kThreads);
+  a.n_blocks = grid.x;
+  if (a.dpre && !a.d_pts && !a.d_ro && !a.d_rd)   // training, no geometry gradient wanted
+    return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+      hipLaunchKernelGGL((x3::field_x3_bwd_kernel<M.value, true, true>), grid, b, 0, st, a);
+    });
+  if (a.dpre)
+    return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+      hipLaunchKernelGGL((x3::field_x3_bwd_kernel<M.value, true>), grid, b, 0, st, a);
+    });
+  if (a.gc_part)   // the eval backward without float atomics (cn_field_backward_fused_ws)
+    return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+      hipLaunchKernelGGL((x3::field_x3_bwd_kernel<M.value, false, false, true>), grid, b, 0, st, a);
+    });
+  return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+    hipLaunchKernelGGL((x3::field_x3_bwd_kernel<M.value>), grid, b, 0, st, a);
+  });
 }
 
 int launch_field_x3(int mode, FieldArgs& a, hipStream_t st) {
-  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(a.m, x3::kTile), cu_count()));
-  if (a.masks && a.save) {
-    switch (mode) {
-      case kFromPts: hipLaunchKernelGGL((x3::field_x3_kernel<kFromPts, true, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-      case kFromRayZ: hipLaunchKernelGGL((x3::field_x3_kernel<kFromRayZ, true, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-      default: return CN_EUNSUPPORTED;
-    }
-    return cn::launch_status();
-  }
-  if (a.masks) {
-    switch (mode) {
-      case kFromPts: hipLaunchKernelGGL((x3::field_x3_kernel<kFromPts, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-      case kFromRayZ: hipLaunchKernelGGL((x3::field_x3_kernel<kFromRayZ, true>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-      default: return CN_EUNSUPPORTED;
-    }
-    return cn::launch_status();
-  }
-  switch (mode) {
-    case kFromPts: hipLaunchKernelGGL((x3::field_x3_kernel<kFromPts, false>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-    case kFromRayZ: hipLaunchKernelGGL((x3::field_x3_kernel<kFromRayZ, false>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-    default: hipLaunchKernelGGL((x3::field_x3_kernel<kFromEncoded, false>), dim3(grid), dim3(x3::kThreads), 0, st, a); break;
-  }
-  return cn::launch_status();
+  const dim3 grid(cn::persistent_grid(a.m, x3::kTile)), b(x3::kThreads);
+  if (a.masks && a.save)
+    return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+      hipLaunchKernelGGL((x3::field_x3_kernel<M.value, true, true>), grid, b, 0, st, a);
+    });
+  if (a.masks)
+    return launch_ray_mode(mode, CN_EUNSUPPORTED, [&](auto M) {
+      hipLaunchKernelGGL((x3::field_x3_kernel<M.value, true>), grid, b, 0, st, a);
+    });
+  return launch_any_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL((x3::field_x3_kernel<M.value, false>), grid, b, 0, st, a);
+  });
 }
 
 }  // namespace mlp

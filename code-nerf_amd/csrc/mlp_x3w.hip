@@ -27,7 +27,8 @@
 // 1 KiB (64 lanes x 16 B) = 32 KiB, fragment f = 2 ob + part at quads f*64 + lane (a wave's
 // ds_read_b128 of one fragment is 1 KiB contiguous, conflict free).  36 chunks (xyz1 2 |
 // xyz2 8 | fc_out 8 | dir1 8 | view-dir 1 | dir2 8 | rgb 1: fragments 2t + part of block 0
-// over its 8 k-steps) = 1.15 MB, the same stream as the fp32 w16 kernel, through the same
+// over its 8 k-steps) = 1.15 MB, the same stream as the fp32 w16 kernel (its layout, constants
+// and encoding maps are the one definition in mlp_stream.h), through the same
 // 4-slot LDS ring (LDS-DMA, 4 pieces per wave per chunk, one barrier in mid-chunk; cyclic
 // across tiles).  A chunk is 8 groups of 2 output blocks: 4 A reads and 6 MFMAs per group,
 // the next group's reads in flight during the current group's MFMAs.
@@ -43,62 +44,30 @@
 // it runs 1.22-1.26 ms (the 32x32x16 kernel 1.17).  Both forms therefore sit at the same
 // ~25-27 GB/s per CU of weight stream.  Kept as the opt-in format "bf16x3_w16" (parity-tested
 // like every field kernel); "bf16x3" stays on mlp_x3.hip.
-#include <algorithm>
-
-#include "mlp_common.h"
+#include "mlp_stream.h"
 
 namespace cn {
 namespace mlp {
 namespace x3w {
 
+using namespace stream;
+using namespace stream16;
+
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-constexpr int kWaves = 8;
-constexpr int kThreads = 64 * kWaves;
-constexpr int kTile = 16 * kWaves;         // samples per workgroup tile
-constexpr int kChunkQuads = 32 * 64;       // 32 fragments x 64 lanes x 16 B = 32 KiB
-constexpr int kRing = 4;
-constexpr int kPiecesPerWave = kChunkQuads / (64 * kWaves);   // 4 x 1 KiB per wave per chunk
-constexpr int kCL2 = 2, kCL3 = 10, kCL4 = 18, kCDir = 26, kCL5 = 27, kCRgb = 35, kChunks = 36;
-constexpr int kStreamFloats = kChunks * kChunkQuads * 4;
-// constants after the stream (as the w16 pack): b_xyz1 | b_dir1 | b_dir2 | sigma weights
-// [g][ob][r] = W_out[0][16 ob + 4 g + r]
-constexpr int kCB1 = 0, kCBD1 = 256, kCBD2 = 512, kCSig = 768, kConsts = 1024;
+// the stream layout, its constants (as the w16 pack) and the encoding maps: stream16 (mlp_stream.h)
 constexpr int kPackedFloats = kStreamFloats + kConsts;
 constexpr int kLdsQuads = kRing * kChunkQuads + (kConsts + kWaves * kCbStride) / 4;
 
-static_assert(kChunks % kRing == 0, "cyclic stream: chunk c + 36 reuses chunk c's ring slot");
-static_assert(kPiecesPerWave == 4, "4 DMA wave-instructions per chunk per wave");
 static_assert(kLdsQuads * 16 <= 160 * 1024, "LDS budget");
 
 // ---------------------------------------------------------------- feature maps
 
 // Input feature of a 256-wide layer fed at k-step t by lane group g, element e.
 __host__ __device__ constexpr int col_b(int t, int g, int e) { return 16 * (2 * t + (e >> 2)) + 4 * g + (e & 3); }
-
-// xyz / view-direction encoding columns: the w16 kernel's maps (mlp_f32.hip), 4-wide k-step
-// 8t + e of the w16 order = element e of 32-wide k-step t here.
-__host__ __device__ constexpr int col_enc_xyz(int t, int g) {
-  const int i = t & 7, p = 4 * i + g;
-  if (p < 30) return (t < 8 ? 3 : 6) + 6 * (p / 3) + p % 3;
-  return t < 8 ? (g == 2 ? 0 : 2) : (g == 2 ? 1 : -1);
-}
-__host__ __device__ constexpr int col_enc_dir(int s, int g) {
-  if (s < 6) {
-    const int p = 4 * (s % 3) + g;
-    return (s < 3 ? 3 : 6) + 6 * (p / 3) + p % 3;
-  }
-  return (s == 6 && g < 3) ? g : -1;
-}
-
-__device__ __forceinline__ unsigned short bf16_bits(float x) {
-  return __builtin_bit_cast(unsigned short, static_cast<__bf16>(x));
-}
 
 // ---------------------------------------------------------------- packing
 
@@ -197,10 +166,6 @@ __device__ __forceinline__ void to_operands(State& s) {
   }
 }
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return static_cast<unsigned>(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) void*)p));
-}
-
 // sigma's h2 part: fc_out row 0 . relu(acc) in fp32 (exact products), before the split.  The
 // weights are loop-invariant LDS reads: volatile asm keeps LLVM from hoisting all 64 of them
 // out of the layer loop (64 registers live across every layer: spills).
@@ -238,12 +203,8 @@ __device__ __forceinline__ void dma_chunk(const State& s, float4* lds, int cn) {
   for (int p = 0; p < kPiecesPerWave; ++p) dma_piece(s, lds, cn, p);
 }
 
-// M_c: chunk c+1 landed for every wave (all but this wave's 4 youngest DMA pieces --
-// chunk c+2's -- retired), every wave past chunk c-1, this wave's LDS reads returned.
-__device__ __forceinline__ void chunk_barrier() {
-  asm volatile("s_waitcnt vmcnt(4)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
+// M_c is chunk_barrier<kMidOut>: chunk c+2's 4 pieces are the younger ones.
+constexpr int kMidOut = 4;
 
 // A fragments {hi, lo} of blocks 2G, 2G+1 of the chunk at `slot` (float4 units, lane applied).
 template <int G>
@@ -290,7 +251,7 @@ __device__ __forceinline__ void chunk16(State& s, float4* lds, int c, bf16x8 bh,
     group_pattern();                                                      \
     __builtin_amdgcn_sched_barrier(0);                                    \
     if constexpr ((G) == 3) {                                             \
-      chunk_barrier();                                                    \
+      chunk_barrier<kMidOut>();                                           \
       dma_chunk(s, lds, c + 3);                                           \
     }                                                                     \
   }
@@ -471,7 +432,7 @@ __device__ __forceinline__ void field_tile(State& s, const FieldArgs& a, float4*
     group_pattern();                                                             \
     __builtin_amdgcn_sched_barrier(0);                                           \
     if constexpr ((G) == 1) {                                                    \
-      chunk_barrier();                                                           \
+      chunk_barrier<kMidOut>();                                                  \
       dma_chunk(s, lds, c + 3);                                                  \
     }                                                                            \
   }
@@ -529,17 +490,6 @@ __global__ __launch_bounds__(kThreads, 2) void field_x3w_kernel(FieldArgs a) {
 
 }  // namespace x3w
 
-static int64_t cu_count_x3w() {
-  static int n[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (n[dev] == 0) {
-    int v = 0;
-    n[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return n[dev];
-}
-
 int64_t packed_floats_x3w() { return x3w::kPackedFloats; }
 
 int launch_pack_x3w(const Params& P, float* packed, hipStream_t st) {
@@ -550,14 +500,10 @@ int launch_pack_x3w(const Params& P, float* packed, hipStream_t st) {
 
 int launch_field_x3w(int mode, FieldArgs& a, hipStream_t st) {
   if (a.masks || a.save) return CN_EUNSUPPORTED;  // inference only: masks / planes come from mlp_x3.hip
-  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(cn::ceil_div(a.m, x3w::kTile), cu_count_x3w()));
-  const dim3 b(x3w::kThreads);
-  switch (mode) {
-    case kFromPts: hipLaunchKernelGGL((x3w::field_x3w_kernel<kFromPts>), dim3(grid), b, 0, st, a); break;
-    case kFromRayZ: hipLaunchKernelGGL((x3w::field_x3w_kernel<kFromRayZ>), dim3(grid), b, 0, st, a); break;
-    default: hipLaunchKernelGGL((x3w::field_x3w_kernel<kFromEncoded>), dim3(grid), b, 0, st, a); break;
-  }
-  return cn::launch_status();
+  const dim3 grid(cn::persistent_grid(a.m, x3w::kTile)), b(x3w::kThreads);
+  return launch_any_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL(x3w::field_x3w_kernel<M.value>, grid, b, 0, st, a);
+  });
 }
 
 }  // namespace mlp
