@@ -6,19 +6,46 @@ With small-integer weights, biases, codes and inputs every product and every par
 network is an integer; while the sum of the terms' magnitudes stays below 2^24, fp32 holds every
 partial sum exactly in ANY summation order (MFMA tiles, butterflies, atomics).  A 3xbf16 product
 Ah.Bh + Ah.Bl + Al.Bh drops only Al.Bl, so it is exact when one operand is a bf16 number (Al = 0:
-every weight here is) or, for the dW GEMMs whose operands are both activations, when no term has two
-operands with a bf16 low part; a value splits exactly into hi + lo when it is an integer below 2^16.
+every weight of the integer models is) or, for the dW GEMMs whose operands are both activations, when
+no term has two operands with a bf16 low part; a value splits exactly into hi + lo when it is an
+integer below 2^16.
 check_exact() asserts those conditions on the float64 reference alone; tests/test_exact_cases_cpu.py
 proves them (and that the fp32 oracle returns the reference bit for bit), tests/test_gpu_field_exact.py
 runs the kernels.  Everything here is CPU torch / numpy; builders are seeded, references are computed
 once per case and must not be modified.
+
+Low weight fragments.  With bf16 weights the third product of every 3xbf16 group multiplies zeros, so
+the models "split:<layer>" give the nonzero weights of ONE GEMM layer a bf16 low part (nine or ten
+significant bits, dyadic: multiples of the unit u = 2^-8) and the argument above is restated in units
+of u:
+  - every quantity of the reference -- planes, pre-activations, raw, code_bias, the masked layer
+    gradients, parameter gradients, g_code, dz and the input gradients -- is a multiple of u (the
+    other layers' weights, the biases, codes, inputs and d_raw stay integers), and every bounded sum of
+    |terms|, divided by u, stays below 2^24: fp32 again holds every partial sum in any order;
+  - every 3xbf16 operand (x, h1, h2, feat, v1, v2, code_bias, every masked layer gradient and the
+    weights) splits exactly, hi = bf16(v), lo = bf16(v - hi), hi + lo == v, both rounded to nearest
+    even as the packs and the kernels round them; check_exact makes that split and compares (a
+    multiple of u is no integer below 2^16, so that shortcut is not used for these models);
+  - no term has two low parts, which is all that Ah.Bh + Ah.Bl + Al.Bh drops: forward, per layer, no
+    input with a low part meets a weight with one; dX, per layer, no masked gradient with a low part
+    meets such a weight; dW, as before, no masked gradient with a low part meets an input with one.
+    In the split layer itself the inputs that meet its weights are therefore bf16 numbers, so Wl.Xl in
+    place of Wl.Xh would lose exactly what dropping Wl.Xh loses;
+  - fc_out row 0 (sigma) is an fp32 dot product in every kernel and stays a bf16 row.
+So on a split model the lo fragments of the packs, the operand the lo product reads and the weight
+split inside the unfused backward's GEMMs are compared bit for bit like everything else, forward and
+backward.  x3_raw() / x3_swapped_lo() emulate the three-product rule in float64:
+tests/test_exact_cases_cpu.py shows with them that the rule returns the reference exactly, and that a
+dropped or misread lo product, or the lo parts of two neighbouring rows or columns changing places,
+changes raw.
 
 Geometry cases (points / rays instead of encoded rows): sin / cos encodings are not integers, so
 geometry models carry zero weights on every sin / cos column of layer_xyz1 and layer_dir1 (finite x 0
 is exactly 0 in every format); points, origins and depths are small integers and ray directions
 +-e_i times a length in {1, 2, 4}, so ro + rd z, |rd|, rd / |rd| and its gradient are exact.  The
 gradients of layer_xyz1 / layer_dir1 with respect to those zero sin / cos columns are sums of
-non-integers and are NOT exact: exact_columns() names the columns a geometry case compares.
+non-integers and are NOT exact: exact_columns() names the columns a geometry case compares.  Ray
+gradients are multiples of 1 / |rd| >= 1/4 (of u / 4 on a split model).
 """
 import zlib
 from collections import OrderedDict
@@ -55,6 +82,31 @@ NNZ_THIN = {k: 2 for k in NNZ}
 NNZ_THIN["fc_rgb"] = 32
 NNZ_SIGMA_THIN = 16
 DENSE_MODELS = tuple("dense:" + k for k in NNZ)
+# Every weight above is a bf16 number, so the third product of a 3xbf16 group (Wl.Xh) multiplies zeros.
+# Model "split:<layer>" (one of a set: "split:<layer>:<j>") gives the nonzero weights of one GEMM layer a
+# bf16 low part: +-(1|2) +- (1|2)/256 (the four of those that need nine or ten significant bits: 1 + 2/256,
+# 1 - 1/256, 1 - 2/256 and 2 - 2/256 are bf16 numbers), multiples of the unit U = 2^-8.  Every
+# other layer stays thin with bf16 weights (some in +-1 only, where the magnitudes would otherwise outgrow an
+# exact hi + lo split); fc_out row 0 (sigma, an fp32 dot product in every kernel) stays a bf16 row.
+U = 2.0 ** -8
+SPLIT_VALUES = np.array([257, 511, 513, 514]) * U    # those of (1|2) +- (1|2)/256 that are no bf16 numbers
+SPLIT_LAYERS = ("layer_xyz1", "layer_xyz2", "fc_out", "layer_dir1", "layer_dir2", "fc_rgb")
+# Models in a layer's set.  One model covers every row and column of a 256-row layer, but behind thin layers
+# some units are dead on every row of a case, and a wrong fragment in front of them would not reach raw: two
+# models, so that every pair of neighbouring rows and columns is seen in raw (test_exact_cases_cpu).  fc_rgb's
+# 3 rows cannot fill 512 columns in one model and keep the rgb sums small.
+SPLIT_COUNT = {k: 2 for k in SPLIT_LAYERS}
+SPLIT_COUNT["fc_rgb"] = 4
+SPLIT_NNZ = {k: 4 for k in SPLIT_LAYERS}
+SPLIT_NNZ["fc_rgb"] = 64
+SPLIT_MODELS = tuple("split:" + k if SPLIT_COUNT[k] == 1 else f"split:{k}:{j}"
+                     for k in SPLIT_LAYERS for j in range(SPLIT_COUNT[k]))
+# (layer, geometry) -> the layers of that model whose bf16 weights are drawn from +-1 alone.  Geometry: point
+# coordinates reach 23, and with +-{1, 2} the activations behind the split layer outgrow an exact hi + lo
+# split (about 2^16 units); fc_rgb: every v2 it reads must be a bf16 number, an integer of 8 significant bits.
+SPLIT_ONES = {(k, True): tuple(NNZ) for k in SPLIT_LAYERS}
+SPLIT_ONES[("fc_rgb", False)] = tuple(NNZ)
+SPLIT_SEED = {("layer_xyz2", True): 1}           # redrawn until check_exact holds on every case of the set
 
 
 def _rng(*key) -> np.random.Generator:
@@ -97,6 +149,9 @@ def probe_model(index, geometry: bool = False) -> "OrderedDict[str, torch.Tensor
     key = (index, geometry)
     if key in _MODELS:
         return _MODELS[key]
+    if isinstance(index, str) and index.startswith("split:"):
+        _MODELS[key] = _split_model(index, geometry)
+        return _MODELS[key]
     rng = _rng("model", index, geometry)
     dense = index[len("dense:"):] if isinstance(index, str) else None
     nnz, nnz_sigma = (NNZ_THIN, NNZ_SIGMA_THIN) if dense else (NNZ, NNZ_SIGMA)
@@ -117,6 +172,52 @@ def probe_model(index, geometry: bool = False) -> "OrderedDict[str, torch.Tensor
         out[name + ".weight"] = torch.from_numpy(w)
         out[name + ".bias"] = torch.from_numpy(rng.integers(-2, 3, size=o).astype(np.float32))
     _MODELS[key] = out
+    return out
+
+
+def split_name(model):
+    """("split:<layer>" | "split:<layer>:<j>") -> (layer, j, models in the layer's set); None for other models."""
+    if not (isinstance(model, str) and model.startswith("split:")):
+        return None
+    parts = model.split(":")
+    return parts[1], int(parts[2]) if len(parts) > 2 else 0, SPLIT_COUNT[parts[1]]
+
+
+def split_set(layer: str):
+    return tuple(m for m in SPLIT_MODELS if split_name(m)[0] == layer)
+
+
+def _split_model(name: str, geometry: bool):
+    """Model "split:<layer>[:<j>]" (see SPLIT_MODELS): the named layer holds SPLIT_NNZ weights per row in
+    +-SPLIT_VALUES, then one more in every allowed column the rows left empty (of a set of several
+    models: in the columns c % (models in the set) == j), fc_out row 0 excepted; every other layer is thin
+    (NNZ_THIN per row in +-{1, 2}, or +-1 for SPLIT_ONES, then its empty columns) and biases are in -1..1."""
+    layer, j, count = split_name(name)
+    rng = _rng("model", name, geometry, SPLIT_SEED.get((layer, geometry), 0))
+    ones = SPLIT_ONES.get((layer, geometry), ())
+    out = OrderedDict()
+
+    def draw(split: bool, only_ones: bool, size: int):
+        sign = rng.choice([-1.0, 1.0], size=size)
+        if split:
+            return (sign * rng.choice(SPLIT_VALUES, size=size)).astype(np.float32)
+        return (sign * (1.0 if only_ones else rng.choice([1.0, 2.0], size=size))).astype(np.float32)
+    for lname, (o, i) in synthetic.layer_shapes().items():
+        cols = allowed_columns(lname, i, geometry)
+        split = lname == layer
+        k = min(SPLIT_NNZ[lname] if split else NNZ_THIN[lname], max(1, len(cols) - 1))
+        w = np.zeros((o, i), dtype=np.float32)
+        for r in range(o):
+            sigma = lname == "fc_out" and r == 0
+            kr = max(k, NNZ_SIGMA_THIN) if sigma else k
+            w[r, rng.choice(cols, size=kr, replace=False)] = draw(split and not sigma, lname in ones, kr)
+        empty = cols[(w[int(lname == "fc_out"):, cols] != 0).sum(axis=0) == 0]
+        if split:
+            empty = empty[empty % count == j]
+        for c in empty:
+            w[rng.integers(int(lname == "fc_out"), o), c] = draw(split, lname in ones, 1)[0]
+        out[lname + ".weight"] = torch.from_numpy(w)
+        out[lname + ".bias"] = torch.from_numpy(rng.integers(-1, 2, size=o).astype(np.float32))
     return out
 
 
@@ -246,7 +347,26 @@ def unfused_backward_cases():
 
 
 def backward_cases():
-    return fused_backward_cases() + unfused_backward_cases()
+    return fused_backward_cases() + unfused_backward_cases() + split_encoded_cases() + split_geometry_cases()
+
+
+def split_encoded_cases():
+    """Low weight fragments, encoded rows: every split model at m = 257; forward and the unfused backward."""
+    return [encoded_case(name, 257, "index") for name in SPLIT_MODELS]
+
+
+def split_geometry_cases():
+    """Low weight fragments, geometry (forwards and fused backwards): per layer and mode the whole-waves-per-ray
+    shape (3, 64, 2) with one code row and with a code row per ray, and (37, 8, 10) with one code row; a
+    layer's set of several models is spread over the cases."""
+    out = []
+    for layer in SPLIT_LAYERS:
+        names = split_set(layer)
+        shapes = (((3, 64, 2), "one"), ((3, 64, 2), "index"), ((37, 8, 10), "one"))
+        for i, mode in enumerate(("pts", "rayz")):
+            out += [geometry_case(names[(3 * i + k) % len(names)], mode, *shape, layout)
+                    for k, (shape, layout) in enumerate(shapes)]
+    return out
 
 
 def all_cases():
@@ -386,34 +506,76 @@ def _is_bf16(t: torch.Tensor) -> torch.Tensor:
     return t.float().bfloat16().double() == t.double()
 
 
-def _integers(t: torch.Tensor) -> bool:
+def _integers(t: torch.Tensor, unit: float = 1.0) -> bool:
+    """Every value is a multiple of ``unit`` (a power of two, so the division is exact)."""
+    t = t / unit
     return bool((t == t.round()).all())
+
+
+def split_bf16(t: torch.Tensor):
+    """hi = bf16(v), lo = bf16(v - hi), both rounded to nearest even as the kernels and the packs round
+    them -> (hi, lo) in float64."""
+    v = t.float()
+    hi = v.bfloat16().float()
+    lo = (v - hi).bfloat16().float()
+    return hi.double(), lo.double()
+
+
+def _splits(t: torch.Tensor) -> torch.Tensor:
+    hi, lo = split_bf16(t)
+    return (t.float().double() == t.double()) & (hi + lo == t.double())
+
+
+def case_unit(case) -> float:
+    """The unit every quantity of the case's reference is a multiple of: 1, or U for a split model."""
+    return U if split_name(case["key"][1]) else 1.0
 
 
 def check_exact(case, backward: bool = True) -> dict:
     """Assert, on the float64 reference alone, every condition of the module docstring (``backward`` False:
-    those of the forward only, for a case no backward runs on); returns the largest magnitude sum and the
-    largest 3xbf16 operand seen (for the record)."""
+    those of the forward only, for a case no backward runs on); returns the largest magnitude sum (in units
+    of the case's unit) and the largest 3xbf16 operand seen (for the record)."""
     ref = reference(case)
     geo = case["geometry"]
+    split = split_name(case["key"][1])
+    u = case_unit(case)
     P = {k: v.double() for k, v in case["params"].items()}
     W = lambda n: P[n + ".weight"]   # noqa: E731
     B = lambda n: P[n + ".bias"]     # noqa: E731
     top = {"sum": 0.0, "x3": 0.0}
 
     def sums(what, s):
-        v = float(s.abs().max()) if s.numel() else 0.0
+        v = float(s.abs().max()) / u if s.numel() else 0.0
         top["sum"] = max(top["sum"], v)
-        assert v < LIMIT_SUM, f"{case['key']} {what}: sum of |terms| {v:.4g} >= 2^24"
+        assert v < LIMIT_SUM, f"{case['key']} {what}: sum of |terms| / unit {v:.4g} >= 2^24"
 
     def x3(what, t):
         v = float(t.abs().max()) if t.numel() else 0.0
         top["x3"] = max(top["x3"], v)
-        assert v < LIMIT_X3, f"{case['key']} {what}: 3xbf16 operand {v:.4g} >= 2^16"
+        if split:
+            # a multiple of U need not be an integer below 2^16: the split itself, as the kernels make it
+            assert bool(_splits(t).all()), f"{case['key']} {what}: a 3xbf16 operand is not hi + lo exactly"
+        else:
+            assert v < LIMIT_X3, f"{case['key']} {what}: 3xbf16 operand {v:.4g} >= 2^16"
 
-    # weights: bf16 numbers (Wl = 0), integers like biases and codes
-    for k, v in P.items():
-        assert bool(_is_bf16(v).all()) and _integers(v), k
+    def low(t):
+        return (~_is_bf16(t)).double()
+
+    if split:
+        # weights: the named layer's nonzeros carry a bf16 low part (fc_out row 0 excepted), are multiples of
+        # U and split exactly; every other weight is a bf16 integer, like biases and codes
+        for k, v in P.items():
+            if k == split[0] + ".weight":
+                body = v[1:] if split[0] == "fc_out" else v
+                assert _integers(v, u) and bool(_splits(v).all()), k
+                assert not bool(_is_bf16(body)[body != 0].any()), k
+                assert bool(_is_bf16(v[:1]).all()) or split[0] != "fc_out", k
+            else:
+                assert bool(_is_bf16(v).all()) and _integers(v), k
+    else:
+        # weights: bf16 numbers (Wl = 0), integers like biases and codes
+        for k, v in P.items():
+            assert bool(_is_bf16(v).all()) and _integers(v), k
     assert _integers(case["zs"]) and _integers(case["zt"]) and _integers(case["d_raw"])
     x = ref["x"]
     xin = x
@@ -434,7 +596,7 @@ def check_exact(case, backward: bool = True) -> dict:
     code, acts = ref["code"], ref["acts"]
     zs, zt = case["zs"].double(), case["zt"].double()
     for t in list(ref["planes"]) + list(ref["pre"].values()) + [ref["raw"], ref["code_bias"]]:
-        assert _integers(t)
+        assert _integers(t, u)
 
     # forward: every accumulated output, sum of |terms| (any partial sum in any order is bounded by it)
     def lin(what, inp, w, b):
@@ -454,17 +616,33 @@ def check_exact(case, backward: bool = True) -> dict:
     lin("v2", v1, W("layer_dir2"), B("layer_dir2"))
     sums("rgb", v2.abs() @ W("fc_rgb")[:, :HID].abs().t() + cbr[:, 513:516])
     # forward: what a 3xbf16 product reads next to a (bf16) weight
-    for what, t in (("x", x), ("h1", h1), ("h2", h2), ("feat", feat), ("v1", v1), ("v2", v2),
-                    ("code_bias", ref["code_bias"])):
+    # (a split model's test is of the values themselves: of a geometry case's x only the raw-input columns,
+    # the sin / cos columns meet zeros in both fragments of every weight)
+    for what, t in (("x", x[:, live] if geo and split else x), ("h1", h1), ("h2", h2), ("feat", feat), ("v1", v1),
+                    ("v2", v2), ("code_bias", ref["code_bias"])):
         x3(what, t)
+    # forward, 3xbf16: Xl.Wl is dropped, so no term may pair an input's low part with a weight's
+    layers = (("layer_xyz1", x[:, :63], W("layer_xyz1")), ("layer_xyz2", h1, W("layer_xyz2")[:, :HID]),
+              ("fc_out", h2, W("fc_out")[:, :HID]),
+              ("layer_dir1", torch.cat((feat, x[:, 63:]), dim=-1), W("layer_dir1")),
+              ("layer_dir2", v1, W("layer_dir2")), ("fc_rgb", v2, W("fc_rgb")[:, :HID]))
+    for name, inp, w in layers:
+        x3("W " + name, w)
+        both = low(inp) @ low(w).t()
+        assert float(both.max()) == 0.0, f"{case['key']} {name}: a forward term with two bf16 low parts"
 
     if not backward:
         return top
     # backward: the masked layer gradients (3xbf16 operands), the dX sums, the dW sums over rows, g_code
     d = ref["dpre"]
     for k, t in d.items():
-        assert _integers(t), k
+        assert _integers(t, u), k
         x3("d " + k, t)
+    # dX, 3xbf16: dpre_l.Wl is dropped
+    for name, g in (("layer_xyz1", d["h1"]), ("layer_xyz2", d["h2"]), ("fc_out", d["out"]), ("layer_dir1", d["v1"]),
+                    ("layer_dir2", d["v2"]), ("fc_rgb", d["rgb"])):
+        both = low(g) @ low(W(name))
+        assert float(both.max()) == 0.0, f"{case['key']} dX {name}: a term with two bf16 low parts"
     sums("d v2", d["rgb"].abs() @ W("fc_rgb")[:, :HID].abs())
     sums("d v1", d["v2"].abs() @ W("layer_dir2").abs())
     sums("d feat|view", d["v1"].abs() @ W("layer_dir1").abs())
@@ -495,8 +673,9 @@ def check_exact(case, backward: bool = True) -> dict:
     for g, a in ((d["s1"], zs), (d["s2"], zs), (d["t1"], zt), (ref["g_code"][:, 0:256], acts["s1"]),
                  (ref["g_code"][:, 256:513], acts["s2"]), (ref["g_code"][:, 513:516], acts["t1"])):
         sums("code dW", g.abs().t() @ a.abs())
-    for t in (ref["dz_s"], ref["dz_t"], ref["g_code"]):
-        assert _integers(t)
+    compared = tuple(ref["grads"][k][..., exact_columns(k, geo) or slice(None)] for k in ref["grads"])
+    for t in (ref["dz_s"], ref["dz_t"], ref["g_code"]) + compared:
+        assert _integers(t, u)
     if geo:
         # d pts = d x[:, 0:3] (the sin / cos columns' gradients are 0 x finite); d ro = sum_s d pts,
         # d rd = sum_s d pts z + the Q1 rows' d vd / |rd| with the radial part removed
@@ -508,10 +687,113 @@ def check_exact(case, backward: bool = True) -> dict:
         sums("d rd", 4 * ((dx * case["z"].double()[..., None]).sum(1) * (case["mode"] == "rayz") + 2 * q1))
         for k in ("d_pts", "d_ro", "d_rd"):
             if k in ref:
-                assert bool((ref[k] * 4 == (ref[k] * 4).round()).all()), k     # multiples of 1 / |rd| >= 1/4
+                assert _integers(ref[k], u / 4), k     # multiples of unit / |rd|, |rd| <= 4
     else:
-        assert _integers(ref["d_x"])
+        assert _integers(ref["d_x"], u)
     return top
+
+
+# ---------------------------------------------------------------------------------------------
+# the three-product rule in float64, and what a wrong low fragment would change
+# ---------------------------------------------------------------------------------------------
+
+# per-sample GEMM layer -> (the plane it reads, the plane it writes, ReLU behind it)
+_CHAIN = (("layer_xyz1", "x", "h1", True), ("layer_xyz2", "h1", "h2", True), ("fc_out", "h2", "feat", False),
+          ("layer_dir1", "feat", "v1", True), ("layer_dir2", "v1", "v2", True), ("fc_rgb", "v2", "rgb", False))
+
+
+def x3_weight(case, layer: str) -> torch.Tensor:
+    """The block of ``layer``'s weight the field kernels' MFMAs read: the per-sample columns (the code halves
+    go through the fp32 code bias), of fc_out the 256 feature rows (row 0 is an fp32 dot product)."""
+    w = case["params"][layer + ".weight"].double()
+    if layer in ("layer_xyz2", "fc_out", "fc_rgb"):
+        w = w[:, :HID]
+    return w[1:] if layer == "fc_out" else w
+
+
+def _x3_product(inp, w, rule: str):
+    """Wh.Xh + Wh.Xl + Wl.Xh with both operands split as the kernels split them; ``rule`` "drop" leaves the
+    third product out, "lolo" forms Wl.Xl in its place."""
+    xh, xl = split_bf16(inp)
+    wh, wl = split_bf16(w)
+    third = {"x3": xh @ wl.t(), "drop": 0.0, "lolo": xl @ wl.t()}[rule]
+    return xh @ wh.t() + xl @ wh.t() + third
+
+
+def _x3_tail(case, ref, layer: str, pre: torch.Tensor, rows) -> torch.Tensor:
+    """raw (..., rows, 4) from ``layer``'s GEMM result ``pre`` (bias not yet added) on sample rows ``rows``,
+    every later layer by the three-product rule."""
+    P = case["params"]
+    cb = ref["code_bias"][ref["code"]][rows]
+    x = ref["x"][rows]
+    started, h2 = False, ref["planes"][1][rows]
+    for name, _, dst, relu in _CHAIN:
+        if name == layer:
+            started, t = True, pre
+        elif started:
+            t = _x3_product(t, x3_weight(case, name), "x3")
+        else:
+            continue
+        if name == "layer_xyz2":
+            t = t + cb[:, 0:256]
+        elif name == "fc_out":
+            t = t + cb[:, 256:512]
+        elif name == "fc_rgb":
+            t = t + cb[:, 513:516]
+        else:
+            t = t + P[name + ".bias"].double()
+        if relu:
+            t = torch.relu(t)
+        if dst == "h2":
+            h2 = t
+        if dst == "feat":
+            t = torch.cat((t, x[:, 63:].expand(t.shape[:-1] + (27,))), dim=-1)
+    # sigma: fc_out row 0 as an fp32 dot product of the unsplit h2
+    sigma = h2 @ P["fc_out.weight"].double()[0, :HID] + cb[:, 512]
+    return torch.cat((t, sigma.expand(t.shape[:-1]).unsqueeze(-1)), dim=-1)
+
+
+def _x3_input(ref, layer: str, rows) -> torch.Tensor:
+    src = {name: s for name, s, _, _ in _CHAIN}[layer]
+    if src == "x":
+        return ref["x"][rows, :63]
+    if src == "feat":
+        return torch.cat((ref["planes"][2][rows], ref["x"][rows, 63:]), dim=-1)
+    return ref["planes"][PLANES.index(src)][rows]
+
+
+def x3_raw(case, layer: str = "layer_xyz1", rule: str = "x3") -> torch.Tensor:
+    """raw (m, 4) of the case by the three-product rule in float64: ``layer`` by ``rule`` (see _x3_product),
+    every layer behind it by the rule proper.  With layer_xyz1 and "x3": the whole network."""
+    ref = reference(case)
+    rows = slice(None)
+    return _x3_tail(case, ref, layer, _x3_product(_x3_input(ref, layer, rows), x3_weight(case, layer), rule), rows)
+
+
+def x3_swapped_lo(case, layer: str, axis: str, rows: int = 96) -> torch.Tensor:
+    """For every pair of neighbouring output rows (``axis`` "rows": r, r + 1 of x3_weight) or input columns
+    ("cols": c, c + 1) of ``layer``: does raw change, on some of the first ``rows`` sample rows, when the low
+    parts of the pair's weights change places?  -> bool per pair.  Only the third product moves: with
+    T = Xh Wl^T, swapped rows swap two columns of T, swapped columns add (Xh_c - Xh_c+1) (Wl_c+1 - Wl_c)^T."""
+    ref = reference(case)
+    rows = slice(0, min(rows, case["m"]))
+    inp, w = _x3_input(ref, layer, rows), x3_weight(case, layer)
+    base = _x3_product(inp, w, "x3")
+    xh, _ = split_bf16(inp)
+    _, wl = split_bf16(w)
+    third = xh @ wl.t()
+    if axis == "rows":
+        n = w.shape[0] - 1
+        pre = base.repeat(n, 1, 1)
+        r = torch.arange(n)
+        pre[r, :, r] += third[:, 1:].t() - third[:, :-1].t()
+        pre[r, :, r + 1] += third[:, :-1].t() - third[:, 1:].t()
+    else:
+        n = w.shape[1] - 1
+        pre = base + (xh[:, :-1] - xh[:, 1:]).t()[:, :, None] * (wl[:, 1:] - wl[:, :-1]).t()[:, None, :]
+    want = _x3_tail(case, ref, layer, base, rows)
+    got = _x3_tail(case, ref, layer, pre, rows)
+    return (got != want).flatten(1).any(1)
 
 
 def reach(case) -> dict:

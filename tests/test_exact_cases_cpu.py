@@ -2,7 +2,9 @@
 meets the derived exactness conditions, the fp32 oracle returns the float64 reference bit for bit (the
 proof that the inputs are exact, taken on the reference and not on the kernels), the model set covers
 every row and column of every weight matrix, and every case reaches the ties and ragged chunks it is
-built for."""
+built for.  For the split models (a bf16 low part in one layer's weights): the conditions in units of 2^-8,
+the cover of every row and column by a low-part weight, and, with a float64 emulation of the three-product
+rule, that a dropped, misread or misplaced low fragment changes raw."""
 import numpy as np
 import pytest
 import torch
@@ -73,6 +75,87 @@ def test_dense_models_fill_their_layer(model):
     w = E.probe_model(model)[model[len("dense:"):] + ".weight"]
     assert bool((w != 0).all())
     assert float((w[1:] != w[:-1]).double().mean()) > 0.75 and float((w[:, 1:] != w[:, :-1]).double().mean()) > 0.75
+
+
+SPLIT_CASES = E.split_encoded_cases() + E.split_geometry_cases()
+SPLIT_IDS = ["-".join(str(k) for k in c["key"]) for c in SPLIT_CASES]
+
+
+@pytest.mark.parametrize("geometry", [False, True])
+@pytest.mark.parametrize("layer", E.SPLIT_LAYERS)
+def test_split_set_covers_every_row_and_column(layer, geometry):
+    """Over a layer's split set every row (fc_out's sigma row excepted: it must be a bf16 row) and every allowed
+    column holds a weight with a bf16 low part; every nonzero of the layer has one, and every weight of the
+    other layers is a bf16 integer."""
+    models = [E.probe_model(name, geometry) for name in E.split_set(layer)]
+    assert len(models) == E.SPLIT_COUNT[layer]
+    ws = torch.stack([m[layer + ".weight"] for m in models])
+    lowp = ~E._is_bf16(ws)
+    body = slice(1, None) if layer == "fc_out" else slice(None)
+    assert bool(lowp[:, body].any(2).any(0).all()), "a row has no low-part weight in any model"
+    cols = E.allowed_columns(layer, ws.shape[2], geometry)
+    assert bool(lowp.any(1).any(0)[cols].all()), "an allowed column has no low-part weight in any model"
+    assert bool((lowp == (ws != 0))[:, body].all()), "a nonzero weight of the split layer is a bf16 number"
+    rest = np.setdiff1d(np.arange(ws.shape[2]), cols)
+    assert not bool(ws[:, :, rest].any())
+    if layer == "fc_out":
+        assert not bool(lowp[:, 0].any()) and bool(ws[:, 0].any())
+    for m in models:
+        for k, v in m.items():
+            if k != layer + ".weight":
+                assert bool(E._is_bf16(v).all()) and bool((v == v.round()).all()), k
+        # nine or ten significant bits, multiples of 2^-8, and an exact hi + lo
+        w = m[layer + ".weight"].double()
+        assert bool((w / E.U == (w / E.U).round()).all()) and float(w.abs().max()) < 4
+        hi, lo = E.split_bf16(w)
+        assert bool((hi + lo == w).all())
+
+
+def test_case_unit():
+    assert E.case_unit(E.encoded_case(0, 257, "index")) == 1.0 and E.case_unit(SPLIT_CASES[0]) == 2.0 ** -8
+
+
+@pytest.mark.parametrize("case", SPLIT_CASES, ids=SPLIT_IDS)
+def test_split_cases_move_every_raw_channel(case):
+    """Every raw channel is nonzero on at least a quarter of the rows (a condition on the inputs), and the
+    split layer's low parts reach raw: some raw value is no integer."""
+    raw = E.reference(case)["raw"]
+    assert float((raw != 0).double().mean(0).min()) >= 0.25
+    assert bool((raw != raw.round()).any())
+
+
+@pytest.mark.parametrize("case", SPLIT_CASES, ids=SPLIT_IDS)
+def test_three_product_rule_equals_reference(case):
+    """The float64 emulation of the kernels' rule (both operands split, Wh.Xh + Wh.Xl + Wl.Xh per layer, sigma
+    as a plain dot product) returns the reference exactly: nothing the rule drops is nonzero."""
+    assert torch.equal(E.x3_raw(case), E.reference(case)["raw"])
+
+
+@pytest.mark.parametrize("case", SPLIT_CASES, ids=SPLIT_IDS)
+def test_dropped_or_misread_low_product_shows(case):
+    """Sensitivity: with the split layer's Wl.Xh dropped raw changes on at least a quarter of the rows, and
+    with Wl.Xl in its place on the same rows (Xl is no copy of Xh anywhere it matters)."""
+    layer = E.split_name(case["key"][1])[0]
+    want = E.reference(case)["raw"]
+    dropped = (E.x3_raw(case, layer, "drop") != want).any(-1)
+    assert float(dropped.double().mean()) >= 0.25, float(dropped.double().mean())
+    lolo = (E.x3_raw(case, layer, "lolo") != want).any(-1)
+    assert torch.equal(lolo, dropped)
+
+
+@pytest.mark.parametrize("axis", ["rows", "cols"])
+@pytest.mark.parametrize("layer", E.SPLIT_LAYERS)
+def test_swapped_low_parts_show(layer, axis):
+    """Sensitivity: the low parts of two neighbouring output rows, or of two neighbouring input columns, of the
+    split layer's MFMA block changing places changes raw on some row of the encoded case of some model of the
+    layer's set -- for EVERY such pair."""
+    seen = None
+    for name in E.split_set(layer):
+        hit = E.x3_swapped_lo(E.encoded_case(name, 257, "index"), layer, axis)
+        seen = hit if seen is None else seen | hit
+    w = E.x3_weight(E.encoded_case(E.split_set(layer)[0], 257, "index"), layer)
+    assert seen.shape[0] == w.shape[0 if axis == "rows" else 1] - 1
+    assert bool(seen.all()), f"pairs not seen: {(~seen).nonzero().flatten().tolist()}"
 
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)

@@ -10,7 +10,13 @@ ray, code row or mask bit shows as an integer difference.  Code indices stay in 
 
 Geometry cases compare the gradients of layer_xyz1 / layer_dir1 on the raw-input columns only
 (exact_cases.exact_columns): the sin / cos columns' gradients are sums of non-integers by construction of
-the inputs, not through any route of a kernel."""
+the inputs, not through any route of a kernel.
+
+The split models (exact_cases.SPLIT_MODELS) give one GEMM layer's weights a bf16 low part, in units of 2^-8:
+on them the 3xbf16 kernels' third product, Wl.Xh, multiplies the packs' lo fragments (bf16x3, bf16x3_w16, the
+transposed bf16x3_t) or the low parts the unfused backward's GEMMs split off themselves, and one lo element a
+block, a lane half or a k-step off, two swapped, or a lo product read against Xl shows as a difference of
+2^-8s (proven on the CPU: test_exact_cases_cpu).  The fp32 formats run on them as a cross-check."""
 import pytest
 import torch
 
@@ -24,6 +30,11 @@ FX = [float(2 ** k) for k in range(10)]
 FD = [float(2 ** k) for k in range(4)]
 
 _DEV = {}
+# every case list a test below runs, then the split models' cases of the same kind
+TRAIN_FORWARD_CASES = E.train_forward_cases()[1:] + E.split_geometry_cases()
+GEOMETRY_FORWARD_CASES = E.geometry_forward_cases() + E.split_geometry_cases()
+FUSED_BACKWARD_CASES = E.fused_backward_cases() + E.split_geometry_cases()
+UNFUSED_BACKWARD_CASES = E.unfused_backward_cases() + E.split_encoded_cases()
 
 
 def ident(case):
@@ -125,6 +136,20 @@ def test_encoded_forward_dense_layer(dev, fmt, model):
     same(raw, ref["raw"], "raw")
 
 
+@pytest.mark.parametrize("model", E.SPLIT_MODELS)
+@pytest.mark.parametrize("fmt", FORWARD_FORMATS)
+def test_encoded_forward_split_layer(dev, fmt, model):
+    """cn_mlp_forward, m = 257, with one layer's weights carrying a bf16 low part: the lo fragments of the
+    bf16x3 / bf16x3_w16 packs and the B operand the lo product reads; the fp32 formats as a cross-check."""
+    from codenerf import ops
+    case = E.encoded_case(model, 257, "index")
+    d, ref = on_dev(dev, case), E.reference(case)
+    cb = code_bias(dev, case)
+    same(cb, ref["code_bias"], "code_bias")
+    raw = ops.mlp_forward(packed(dev, case, fmt), cb, d["x"], d["code_index"], precision=fmt)
+    same(raw, ref["raw"], "raw")
+
+
 @pytest.mark.parametrize("layout", E.LAYOUTS)
 @pytest.mark.parametrize("m", E.ENCODED_SIZES)
 @pytest.mark.parametrize("fmt", FORWARD_FORMATS)
@@ -179,11 +204,12 @@ def test_encoded_forward_train(dev):
         same(saved[k], ref["planes"][k], "plane " + name)
 
 
-@pytest.mark.parametrize("case", E.train_forward_cases()[1:], ids=ident)
+@pytest.mark.parametrize("case", TRAIN_FORWARD_CASES, ids=ident)
 @pytest.mark.parametrize("precision", ["f32", "bf16x3", "f32_v1"])
 def test_geometry_forward_train(dev, case, precision):
     """cn_radiance_field_train_fmt ("f32": f32_w16, "bf16x3") and cn_radiance_field_train ("f32_v1", no
-    masks): raw, all five planes, and the ReLU masks decoded to the reference's decisions, zeros included."""
+    masks): raw, all five planes, and the ReLU masks decoded to the reference's decisions, zeros included.
+    On the split models' cases the training forward's lo fragments."""
     from codenerf import ops
     d, ref = on_dev(dev, case), E.reference(case)
     r, s, chunk = case["r"], case["s"], case["chunk"]
@@ -208,12 +234,12 @@ def test_geometry_forward_train(dev, case, precision):
 # ---------------------------------------------------------------- 3. geometry forward
 
 
-@pytest.mark.parametrize("case", E.geometry_forward_cases(), ids=ident)
+@pytest.mark.parametrize("case", GEOMETRY_FORWARD_CASES, ids=ident)
 @pytest.mark.parametrize("fmt", FORWARD_FORMATS + ("density",))
 def test_geometry_forward(dev, case, fmt):
     """cn_radiance_field in the four inference formats and cn_density_field, from points and from rays +
     depths: short last chunks, chunks that are no multiple of the tile, the Q1 ray of every row, the code row
-    of every ray."""
+    of every ray.  On the split models' cases the lo fragments of both 3xbf16 packs."""
     from codenerf import ops
     d, ref = on_dev(dev, case), E.reference(case)
     r, s, chunk = case["r"], case["s"], case["chunk"]
@@ -231,13 +257,14 @@ def test_geometry_forward(dev, case, fmt):
 # ---------------------------------------------------------------- 4. backwards
 
 
-@pytest.mark.parametrize("case", E.fused_backward_cases(), ids=ident)
+@pytest.mark.parametrize("case", FUSED_BACKWARD_CASES, ids=ident)
 @pytest.mark.parametrize("deterministic", [True, False])
 @pytest.mark.parametrize("precision", ["f32", "bf16x3"])
 def test_fused_backward_eval(dev, case, precision, deterministic):
     """cn_radiance_field_masks_fmt + cn_field_backward_fused_ws (``deterministic``: with whole waves per ray,
     the (3, 64, 2) shape, its form without float atomics; else, and with deterministic False, the atomic
-    kernel): raw, the masks, g_code, d pts or d ro, d rd.  A tie at 0 gives gradient 0."""
+    kernel): raw, the masks, g_code, d pts or d ro, d rd.  A tie at 0 gives gradient 0.  On the split models'
+    cases the lo fragments of the transposed packs the dX chain streams."""
     from codenerf import ops
     d, ref = on_dev(dev, case), E.reference(case)
     r, s, chunk = case["r"], case["s"], case["chunk"]
@@ -260,11 +287,12 @@ def test_fused_backward_eval(dev, case, precision, deterministic):
         same(out["d_ro"], ref["d_ro"], "d ro")
 
 
-@pytest.mark.parametrize("case", E.fused_backward_cases(), ids=ident)
+@pytest.mark.parametrize("case", FUSED_BACKWARD_CASES, ids=ident)
 @pytest.mark.parametrize("precision", ["f32", "bf16x3"])
 def test_fused_backward_train(dev, case, precision):
     """cn_radiance_field_train_fmt + cn_field_backward_train_multi (one field) + the code backward: every
-    parameter gradient, g_code, d z_s / d z_t, d pts or d ro, d rd."""
+    parameter gradient, g_code, d z_s / d z_t, d pts or d ro, d rd.  On the split models' cases the transposed
+    pack's lo fragments, and dW GEMMs whose operands carry low parts on one side at a time."""
     from codenerf import ops
     d, ref = on_dev(dev, case), E.reference(case)
     r, s, chunk = case["r"], case["s"], case["chunk"]
@@ -292,11 +320,12 @@ def test_fused_backward_train(dev, case, precision):
         same(out["d_ro"], ref["d_ro"], "d ro")
 
 
-@pytest.mark.parametrize("case", E.unfused_backward_cases(), ids=ident)
+@pytest.mark.parametrize("case", UNFUSED_BACKWARD_CASES, ids=ident)
 @pytest.mark.parametrize("precision", ["f32", "bf16x3"])
 def test_unfused_backward_encoded(dev, case, precision):
     """cn_mlp_forward_train + cn_field_backward_fmt on encoded rows + the code backward: d x, every parameter
-    gradient (all columns: the encodings are integers here), g_code, d z_s / d z_t."""
+    gradient (all columns: the encodings are integers here), g_code, d z_s / d z_t.  On the split models the
+    weight split that cn_gemm_nn_x3 makes itself from the fp32 weights."""
     from codenerf import ops
     d, ref = on_dev(dev, case), E.reference(case)
     m, n_codes = case["m"], case["zs"].shape[0]

@@ -118,6 +118,76 @@ def test_gemm_tn_accumulates(dev, m, n, k, precision, det):
         assert torch.equal(c, c2), "deterministic gemm_tn differs between two runs"
 
 
+# Bitwise GEMM probes.  Dyadic operands in units of u = 2^-8: one operand carries a bf16 low part (+-{257, 511,
+# 513, 514} / 256: nine or ten significant bits, hi + lo exact), the other is made of bf16 numbers (+-{1, 2, 3}),
+# so a 3xbf16 product Ah.Bh + Ah.Bl + Al.Bh drops nothing, every term is a multiple of u and, while the sum of
+# the terms' magnitudes stays below 2^24 u, fp32 holds every partial sum exactly in any order: the kernels must
+# return the float64 product's bits.  The tolerances above cannot see one misplaced low part (2^-9 of one term
+# of hundreds); these see it as a difference of whole units.  Each GEMM runs with the low parts in A, then in B.
+GEMM_UNIT = 2.0 ** -8
+
+
+def dyadic(g, shape, low: bool):
+    sign = torch.randint(0, 2, shape, generator=g).double() * 2 - 1
+    if low:
+        v = torch.tensor([257.0, 511.0, 513.0, 514.0], dtype=torch.float64)[torch.randint(0, 4, shape, generator=g)]
+        return sign * v * GEMM_UNIT
+    return sign * torch.randint(1, 4, shape, generator=g).double()
+
+
+def check_dyadic(a, b, terms):
+    """The conditions of the bitwise claim, on the float64 operands: exactly one operand has low parts and it
+    splits into bf16 hi + lo exactly; sum of |terms| / u < 2^24."""
+    def is_bf16(t):
+        return t.float().bfloat16().double() == t
+    assert bool(is_bf16(a).all()) != bool(is_bf16(b).all())
+    for t in (a, b):
+        hi = t.float().bfloat16().double()
+        lo = (t - hi).float().bfloat16().double()
+        assert bool((hi + lo == t).all())
+    assert float(terms.max()) / GEMM_UNIT < 2 ** 24
+
+
+def same_bits(c, ref, what):
+    c = c.cpu()
+    assert torch.equal(c, ref.float()) and torch.equal(c.double(), ref), (
+        f"{what}: {int((c.double() != ref).sum())} of {ref.numel()} values differ; first at "
+        f"{tuple((c.double() != ref).nonzero()[0].tolist())}")
+
+
+@pytest.mark.parametrize("low_in", ["a", "b"])
+@pytest.mark.parametrize("precision", ["f32", "bf16x3"])
+@pytest.mark.parametrize("m,n,k,lda", [(64, 3, 256, None), (300, 63, 3, None), (1000, 257, 283, None),
+                                       (129, 256, 63, 90)])
+def test_gemm_nn_bitwise(dev, m, n, k, lda, precision, low_in):
+    """cn_gemm_nn / cn_gemm_nn_x3, masked, contiguous A and (lda 90) a row-strided A: the float64 product's bits."""
+    from codenerf import ops
+    g = torch.Generator().manual_seed(m + n + k)
+    store = dyadic(g, (m, lda or k), low_in == "a")
+    a, b = store[:, :k], dyadic(g, (k, n), low_in == "b")
+    mask = torch.randn(m, n, generator=g)
+    check_dyadic(a, b, a.abs() @ b.abs())
+    sd = store.float().to(dev)
+    c = ops.gemm_nn(sd[:, :k] if lda else sd, b.float().to(dev), mask.to(dev), precision=precision)
+    same_bits(c, (a @ b) * (mask > 0), f"gemm_nn {precision} low parts in {low_in}")
+
+
+@pytest.mark.parametrize("low_in", ["a", "b"])
+@pytest.mark.parametrize("det", [False, True])
+@pytest.mark.parametrize("precision", ["f32", "bf16x3"])
+@pytest.mark.parametrize("m,n,k", [(33, 3, 256), (5000, 257, 256)])
+def test_gemm_tn_bitwise(dev, m, n, k, precision, det, low_in):
+    """cn_gemm_tn / cn_gemm_tn_x3 / cn_gemm_tn_ws onto a nonzero C: c0 + A^T B in float64, every bit, with float
+    atomics and with the fixed-order reduction."""
+    from codenerf import ops
+    g = torch.Generator().manual_seed(m * 3 + n + k)
+    a, b = dyadic(g, (m, n), low_in == "a"), dyadic(g, (m, k), low_in == "b")
+    c0 = dyadic(g, (n, k), True)
+    check_dyadic(a, b, c0.abs() + a.abs().t() @ b.abs())
+    c = ops.gemm_tn(a.float().to(dev), b.float().to(dev), c0.float().to(dev), precision=precision, deterministic=det)
+    same_bits(c, c0 + a.t() @ b, f"gemm_tn {precision} det={det} low parts in {low_in}")
+
+
 # ---------------------------------------------------------------- element-wise stages
 
 
