@@ -376,18 +376,22 @@ class ObjectRays(torch.autograd.Function):
         return d_ro, d_rd, d_poses, None
 
 
-class CullRows(torch.autograd.Function):
+def _cull_rows(ro, rd, z, chunk_rows, occupancy, holder):
     """ops.occupancy_cull's compact rows -> pts (M', 3), vdir (M', 3); ``holder["state"]`` receives the cull's
-    state (for ExpandRows) and ``holder["count"]`` M'.  Gradients w.r.t. ro and rd (z is detached); the kept
-    set is a constant."""
+    state (for ExpandRows) and ``holder["count"]`` M'."""
+    holder["count"], _, pts, vdir, _, holder["state"] = ops.occupancy_cull(
+        ro, rd, z, chunk_rows, occupancy.bits, occupancy.resolution, occupancy.bound, want_code=False)
+    return pts, vdir
+
+
+class CullRows(torch.autograd.Function):
+    """_cull_rows with gradients w.r.t. ro and rd (z is detached); the kept set is a constant."""
 
     @staticmethod
     def forward(ctx, ro, rd, z, chunk_rows, occupancy, holder):
         ctx.set_materialize_grads(False)
-        count, _, pts, vdir, _, state = ops.occupancy_cull(ro, rd, z, chunk_rows, occupancy.bits, occupancy.resolution,
-                                                          occupancy.bound, want_code=False)
-        holder["state"], holder["count"] = state, count
-        ctx.state, ctx.chunk_rows = state, chunk_rows
+        pts, vdir = _cull_rows(ro, rd, z, chunk_rows, occupancy, holder)
+        ctx.state, ctx.chunk_rows = holder["state"], chunk_rows
         ctx.save_for_backward(z)
         return pts, vdir
 
@@ -470,9 +474,7 @@ def culled_field_autograd(model, ro, rd, z, z_s, z_t, occupancy, fx, fd):
     if _needs_grad(ro, rd):
         pts, vdir = CullRows.apply(ro, rd, z, ro.shape[0], occupancy, holder)
     else:
-        count, _, pts, vdir, _, state = ops.occupancy_cull(ro.detach(), rd.detach(), z, ro.shape[0], occupancy.bits,
-                                                          occupancy.resolution, occupancy.bound, want_code=False)
-        holder["state"], holder["count"] = state, count
+        pts, vdir = _cull_rows(ro.detach(), rd.detach(), z, ro.shape[0], occupancy, holder)
     count = holder["count"]
     if not count:
         return ops.occupancy_expand(None, holder["state"])

@@ -5,8 +5,8 @@ are zeroed by the caller, a workspace's contents on entry are ignored.  ``contra
 properties of that contract that no value comparison sees:
 
   * reading memory nobody wrote.  While the context is active the package modules that allocate for the
-    library (``codenerf.ops``, ``codenerf.autograd``, ``codenerf.nerf``, ``codenerf.optim``,
-    ``codenerf.train``, ``codenerf.evaluate``) see a stand-in
+    library (``codenerf.ops``, ``codenerf.autograd``, ``codenerf.nerf`` and its render modules,
+    ``codenerf.optim``, ``codenerf.train``, ``codenerf.evaluate``) see a stand-in
     for the name ``torch``.  It forwards every attribute to the real module, but ``empty`` / ``empty_like``
     return a tensor whose interior is filled per ``fill``: ``"zero"`` (what fresh device memory usually
     holds) or ``"poison"``: NaN for floating types, the *value* 1 for integer types (``fill_(1)``, not a
@@ -45,7 +45,8 @@ ALIGN = 256
 CANARY = 0xA5
 FILLS = ("zero", "poison")
 PATCHED_MODULES = ("codenerf.ops", "codenerf.autograd", "codenerf.nerf", "codenerf.optim", "codenerf.train",
-                   "codenerf.evaluate")
+                   "codenerf.evaluate") + tuple(
+    "codenerf.nerf." + m for m in ("fields", "density", "mesh", "occupancy", "render", "scene", "distributed"))
 
 
 class GuardError(AssertionError):
