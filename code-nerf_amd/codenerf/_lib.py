@@ -147,6 +147,9 @@ SIGNATURES = {
     "cn_isosurface_workspace_bytes": (_i64, [_i64]),
     "cn_isosurface_count": (_i, [_p, _i64, _f, _p, _p, _p]),
     "cn_isosurface_emit": (_i, [_p, _p, _i64, _f, _p, _i64, _i64, _p, _p, _p]),
+    "cn_surface_bracket": (_i, [_p, _i64, _p, _i64, _i64, _f, _p, _p, _p]),
+    "cn_surface_step": (_i, [_p, _p, _p, _p, _i64, _f, _i, _i64, _p, _p, _p, _p]),
+    "cn_surface_shade": (_i, [_p, _p, _p, _fp, _i64, _p, _p, _p, _p]),
     "cn_radiance_field_train": (_i, [_p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _fp, _fp, _p, _p, _p]),
     "cn_mlp_forward_train": (_i, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p]),
     "cn_encode_inputs": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _fp, _fp, _p, _p]),

@@ -27,10 +27,11 @@ from .position_embed import PositionalEmbedder
 from .ray_sampler import RaySampler
 from .render import forward_pass, predict_radiance_and_render, prepare_embedders, prepare_samplers, render_rays
 from .scene import SceneObject, render_scene, render_scene_autograd, rigid_pose, similarity_pose
+from .surface import render_surface
 from .volumetric_render import volume_render
 
 __all__ = ["RaySampler", "PointSampler", "PositionalEmbedder", "volume_render", "prepare_samplers",
            "prepare_embedders", "predict_radiance_and_render", "forward_pass", "parallel_image_render",
            "render_rays", "gather_rows", "gather_views", "density", "density_grid", "OccupancyGrid", "Mesh", "extract_mesh",
            "density_gradient", "normals", "SceneObject", "render_scene", "render_scene_autograd", "rigid_pose",
-           "similarity_pose"]
+           "similarity_pose", "render_surface"]

@@ -929,6 +929,115 @@ def sample_span(ro: Tensor, rd: Tensor, grids, near: float, far: float, n_probes
     return z, span, probe_range
 
 
+# ------------------------------------------------------------------ iso-surface ray casting
+
+
+def _strided_density(t: Tensor, name: str, shape) -> Tuple[Tensor, int]:
+    """A density the surface entries read in place -> (the tensor, its element stride 1 or 4): ``t`` of ``shape``,
+    contiguous, or column 3 of contiguous (.., 4) raw rows (``raw[..., 3]``); anything else is copied."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor")
+    if t.device.type != "cuda":
+        raise ValueError(f"{name} must be on a HIP device (got {t.device}); the MI355X path has no CPU fallback")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be {torch.float32} (got {t.dtype})")
+    assert tuple(t.shape) == tuple(shape), f"{name} must be {tuple(shape)}"
+    if not t.is_contiguous():
+        rows = 4
+        for k in reversed(range(t.dim())):
+            if t.shape[k] != 1 and t.stride(k) != rows:
+                return t.contiguous(), 1
+            rows *= t.shape[k]
+        return t, 4
+    return t, 1
+
+
+def _out(t: Optional[Tensor], name: str, shape, dtype, device) -> Tensor:
+    """A caller's output buffer, checked, or a fresh one."""
+    if t is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    assert isinstance(t, torch.Tensor) and t.device == device and t.dtype == dtype and \
+        tuple(t.shape) == tuple(shape) and t.is_contiguous(), f"{name} must be a contiguous {dtype} {tuple(shape)}"
+    return t
+
+
+def surface_bracket(sigma: Tensor, z: Tensor, level: float, bracket: Optional[Tensor] = None,
+                    hit: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """Each ray's first crossing of ``sigma >= level`` among its search depths (cn_surface_bracket; the rule is in
+    include/codenerf.h) -> bracket (R, 4) = [t_lo, t_hi, s_lo, s_hi], hit (R,) int32: 0 no crossing (both ends
+    the last sample), 2 the first sample is at or above the level (both ends sample 0), 1 a crossing between
+    samples j - 1 and j.  ``sigma`` (R, S): contiguous, or ``raw[..., 3]`` of contiguous (R, S, 4) rows, read in
+    place; ``z`` (R, S) ascending; S in [2, 1024]; ``level`` finite, in sigma's unit.  ``bracket`` / ``hit``:
+    buffers to write instead of fresh ones.  One launch, graph-capturable."""
+    lib = _lib_ready()
+    z = _cuda(z, "z")
+    assert z.dim() == 2, "z must be (num_rays, num_samples)"
+    n, s = z.shape
+    sigma, stride = _strided_density(sigma, "sigma", (n, s))
+    level = float(level)
+    assert 2 <= s <= 1024, "num_samples must be in [2, 1024]"
+    assert level == level and abs(level) != float("inf"), "level must be finite"
+    bracket = _out(bracket, "bracket", (n, 4), torch.float32, z.device)
+    hit = _out(hit, "hit", (n,), torch.int32, z.device)
+    if n:
+        check(lib.cn_surface_bracket(ptr(sigma), stride, ptr(z), n, s, level, ptr(bracket), ptr(hit), stream_of(z)),
+              "cn_surface_bracket")
+    return bracket, hit
+
+
+def surface_step(ro: Tensor, rd: Tensor, hit: Tensor, bracket: Tensor, level: float, t: Optional[Tensor] = None,
+                 probe: Optional[Tensor] = None, finish: bool = False,
+                 pts: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """One round of the per-ray bisection (cn_surface_step) -> (t (R,), pts (R, 3) = ro + rd t).  ``bracket`` (R, 4)
+    from surface_bracket is updated IN PLACE, and so is ``t`` when given.  ``probe`` (R,): the density at the
+    previous call's ``t`` (contiguous, or ``raw[..., 3]`` of contiguous (R, .., 4) rows), which replaces the end
+    of the bracket on its side of ``level`` where hit == 1; None on the first call, which only places ``t``.
+    Then t = the bracket's midpoint, or with ``finish`` the linear interpolation of ``level`` between its ends
+    (t_hi where the low end's density is unknown or the ends' densities do not rise).  One launch."""
+    lib = _lib_ready()
+    ro, rd, hit = _cuda(ro, "ro"), _cuda(rd, "rd"), _cuda(hit, "hit", torch.int32)
+    n = hit.shape[0]
+    assert hit.shape == (n,) and ro.shape == (n, 3) and rd.shape == (n, 3), \
+        "hit must be (num_rays,) and ro / rd (num_rays, 3)"
+    level = float(level)
+    assert level == level and abs(level) != float("inf"), "level must be finite"
+    bracket = _out(bracket, "bracket", (n, 4), torch.float32, ro.device)
+    assert bracket.data_ptr() % 16 == 0, "bracket must be 16-byte aligned"
+    stride = 1
+    if probe is not None:
+        assert t is not None, "probe is the density at the previous call's t: pass that t"
+        probe, stride = _strided_density(probe, "probe", (n,))
+    t = _out(t, "t", (n,), torch.float32, ro.device)
+    pts = _out(pts, "pts", (n, 3), torch.float32, ro.device)
+    if n:
+        check(lib.cn_surface_step(ptr(ro), ptr(rd), ptr(hit), ptr(probe), stride, level, int(bool(finish)), n,
+                                  ptr(bracket), ptr(t), ptr(pts), stream_of(ro)), "cn_surface_step")
+    return t, pts
+
+
+def surface_shade(raw: Tensor, hit: Tensor, t: Tensor, pts: Tensor, background=(1.0, 1.0, 1.0),
+                  rgb: Optional[Tensor] = None, depth: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """The surface render's outputs from the field's rows at the final points (cn_surface_shade) -> (rgb (R, 3),
+    depth (R,)).  A ray with hit != 0 shows sigmoid(raw[:3]) * 1.002 - 0.001, volume_render's colour of a raw row,
+    at depth ``t``; a ray with hit == 0 shows ``background`` at depth +inf, and its row of ``pts`` (R, 3), written
+    IN PLACE, becomes NaN.  ``raw`` (R, 4) or (R, 1, 4).  One launch."""
+    lib = _lib_ready()
+    raw, hit, t = _cuda(raw, "raw"), _cuda(hit, "hit", torch.int32), _cuda(t, "t")
+    n = hit.shape[0]
+    assert hit.shape == (n,) and t.shape == (n,) and raw.numel() == 4 * n and raw.shape[-1] == 4, \
+        "hit and t must be (num_rays,) and raw (num_rays, 4)"
+    raw = _aligned16(raw)
+    bg = [float(v) for v in background]
+    assert len(bg) == 3, "background must be three floats"
+    pts = _out(pts, "pts", (n, 3), torch.float32, raw.device)
+    rgb = _out(rgb, "rgb", (n, 3), torch.float32, raw.device)
+    depth = _out(depth, "depth", (n,), torch.float32, raw.device)
+    if n:
+        check(lib.cn_surface_shade(ptr(raw), ptr(hit), ptr(t), _lib.host_floats(bg), n, ptr(rgb), ptr(depth),
+                                   ptr(pts), stream_of(raw)), "cn_surface_shade")
+    return rgb, depth
+
+
 # ------------------------------------------------------------------ iso-surface extraction
 
 

@@ -113,4 +113,10 @@ __device__ __forceinline__ float sigmoid_hw(float x) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
 }
 
+// A raw colour channel as it is shown (volumetric_render.py:28): sigmoid(x) * 1.002 - 0.001, the product
+// and the difference each rounded -- what cn_volume_render composites and cn_surface_shade writes.
+__device__ __forceinline__ float widened_sigmoid(float x) {
+  return __fsub_rn(__fmul_rn(sigmoid_hw(x), 1.002f), 0.001f);
+}
+
 }  // namespace cn

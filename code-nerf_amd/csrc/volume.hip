@@ -198,9 +198,7 @@ __device__ __forceinline__ void load_raw_lds(const float4* sl, int q0, int j0, i
 // A raw row's density and colour channel (volumetric_render.py:32 and :28), shared by the plain and the
 // composed render: shifted_softplus(x) = softplus(x - 1); widened_sigmoid(x) = sigmoid(x) * 1.002 - 0.001.
 __device__ __forceinline__ float raw_sigma(float x) { return cn::softplus20(__fsub_rn(x, 1.0f)); }
-__device__ __forceinline__ float raw_colour(float x) {
-  return __fsub_rn(__fmul_rn(cn::sigmoid_hw(x), 1.002f), 0.001f);
-}
+__device__ __forceinline__ float raw_colour(float x) { return cn::widened_sigmoid(x); }
 
 // This lane's run of weights: 16-B stores where the run is aligned (see load_depths).  S: the samples
 // that contribute (0 for the sample-free S_in == 1).

@@ -714,6 +714,55 @@ int cn_isosurface_emit(const float* nodes, const float* axis, int64_t n, float i
                        int64_t max_vertices, int64_t max_faces, float* vertices, int32_t* faces,
                        cn_stream_t stream);
 
+/* --- Iso-surface ray casting (inference) ---------------------------------
+ * Where a ray first meets the level set sigma_raw = level: a search over S ascending depths per ray, then a
+ * bisection of the bracketing pair, then one interpolation.  The densities come from the density entries
+ * (cn_density_field, cn_density_gradient's column 3, cn_occupancy_expand's rows); the three entries here are
+ * the per-ray search around them.  fp32, every operation named below rounded on its own, no FMA.
+ * A value s is KNOWN iff s > CN_EMPTY_SIGMA_RAW: false for a culled slot's marker and for NaN.
+ * A strided density: element i at ptr[i * stride], stride 1 (a plain array) or 4 (column 3 of (.., 4) raw
+ * rows, the pointer passed already offset to that column).
+ *   bracket  j = the smallest s in 0..S-1 with sigma[r][s] >= level (NaN compares false; a tie counts as
+ *            reached).  No such j: hit = 0, lo = hi = S - 1.  j = 0 (the ray starts at or above the level):
+ *            hit = 2, lo = hi = 0.  Otherwise hit = 1, lo = j - 1, hi = j.
+ *            bracket[r] = [t_lo, t_hi, s_lo, s_hi] = [z[r][lo], z[r][hi], sigma[r][lo], sigma[r][hi]].
+ *   step     update (only with a probe, only where hit = 1), sp = probe[r], the density at the previous t[r]:
+ *            sp >= level ? (t_hi, s_hi) = (t, sp) : (t_lo, s_lo) = (t, sp) -- a NaN goes to the low end;
+ *            next depth (finish = 0):  t = t_lo + 0.5f * (t_hi - t_lo);
+ *            final depth (finish = 1): t = t_lo + w * (t_hi - t_lo), w = 1 when s_lo is not known or
+ *            s_hi - s_lo <= 0, else w = min(max((level - s_lo) / (s_hi - s_lo), 0), 1): a true division, and
+ *            a NaN quotient becomes 0 (the max and the min return their other operand);
+ *            hit != 1 has t_lo = t_hi, both forms give that depth;
+ *            point: pts[r][c] = ro[r][c] + rd[r][c] * t, the product and the sum each rounded (cn_ray_points).
+ *   shade    hit != 0: rgb[r][c] = sigmoid(raw[r][c]) * 1.002 - 0.001, the expression cn_volume_render
+ *            composites (the same device function); depth[r] = t[r]; pts[r] is left as it is.
+ *            hit = 0: rgb[r] = background, depth[r] = +inf, pts[r] = NaN.
+ * All three are one launch on `stream` over exactly n_rays rows: no workspace, no atomics, no count read
+ * back, no synchronisation; argument errors return CN_EINVAL before any launch. */
+
+/* The bracket rule.  sigma: strided, element (r, s) at sigma[(r n_samples + s) sigma_stride]; z (n_rays,
+ * n_samples) ascending per ray.  Outputs, every element written: bracket (n_rays, 4), hit (n_rays) int32.
+ * CN_EINVAL: a NULL pointer; n_rays <= 0; n_samples outside 2..1024; level NaN or infinite; sigma_stride
+ * neither 1 nor 4. */
+int cn_surface_bracket(const float* sigma, int64_t sigma_stride, const float* z, int64_t n_rays, int64_t n_samples,
+                       float level, float* bracket, int32_t* hit, cn_stream_t stream);
+
+/* The step rule.  ro, rd (n_rays, 3); hit (n_rays) int32; probe_sigma: strided (n_rays) or NULL (the first
+ * call: no update, t is only written).  bracket (n_rays, 4), 16-byte aligned, and t (n_rays): read and
+ * written in place; pts (n_rays, 3): every element written.
+ * CN_EINVAL: ro, rd, hit, bracket, t or pts NULL; n_rays <= 0; level NaN or infinite; finish neither 0 nor 1;
+ * probe_stride neither 1 nor 4; bracket misaligned. */
+int cn_surface_step(const float* ro, const float* rd, const int32_t* hit, const float* probe_sigma,
+                    int64_t probe_stride, float level, int finish, int64_t n_rays, float* bracket, float* t,
+                    float* pts, cn_stream_t stream);
+
+/* The shade rule.  raw (n_rays, 4), 16-byte aligned: the field's rows at the final points; hit, t (n_rays);
+ * background: three HOST floats.  rgb (n_rays, 3) and depth (n_rays): every element written; pts (n_rays, 3):
+ * only the rows of rays with hit = 0 are written.
+ * CN_EINVAL: a NULL pointer; n_rays <= 0; raw misaligned. */
+int cn_surface_shade(const float* raw, const int32_t* hit, const float* t, const float* background,
+                     int64_t n_rays, float* rgb, float* depth, float* pts, cn_stream_t stream);
+
 /* --- Backward (autograd through the eval / train step) ------------------
  * The gradients loss.backward() takes through the path in the reference's
  * test-time optimisation (view_synthesis/eval.py) and training step:
